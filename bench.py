@@ -15,16 +15,46 @@ Run directly (1 GPU) or under torch.distributed.run with --nproc-per-node N
 
 Reference wall-clock for this workload: 1500 rounds in 00:08:22 ≈ 2.99
 rounds/s on an unspecified GPU (BASELINE.md / reference README.md:39).
+
+A plain run sets up, warms up, times ``--steps`` rounds and prints the
+result line — nothing else.  ``--dump-outputs DIR`` additionally writes
+what the last timed round produced (the global model and the sampled
+clients' training losses) as ``DIR/<name>.npy``; data, initial weights and
+client sampling are seeded, so two builds run with the same arguments can
+be compared output for output.  ``--full`` is where measurements beyond
+the headline figure belong (extra configurations, baselines, per-kernel
+figures); it is off by default.
 """
 
 import argparse
 import json
 import os
+import tempfile
 import time
 
+import numpy as np
 import torch
 
 REF_ROUNDS_PER_SEC = 1500 / 502.0  # reference CNN_FEMNIST: 1500 rounds / 8:22
+DUMP_BUDGET_BYTES = 64 * 10 ** 6  # cap on everything --dump-outputs writes
+
+
+def dump_outputs(out_dir, outputs):
+    """Write ``{name: array}`` as float32/float64 ``<name>.npy`` files under
+    ``out_dir``.  An array over its share of DUMP_BUDGET_BYTES is replaced
+    by a fixed, seeded sample of its flattened elements (same indices on
+    every run)."""
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // max(len(outputs), 1)
+    for name, arr in outputs.items():
+        arr = np.ascontiguousarray(arr)
+        if arr.dtype != np.float64:
+            arr = arr.astype(np.float32, copy=False)
+        if arr.nbytes > share:
+            idx = np.random.default_rng(0).choice(
+                arr.size, size=share // arr.itemsize, replace=False)
+            arr = arr.reshape(-1)[np.sort(idx)]
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
 
 
 def build_config(args):
@@ -100,6 +130,14 @@ def main():
                          "fwd/bwd, fc1 fwd) with fp32 master/accum "
                          "(BASELINE config 2); fp32 matches the "
                          "reference's precision")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed "
+                         "round computed (global model parameters, sampled "
+                         "clients' training losses) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements beyond the headline "
+                         "figure; a plain run only sets up, warms up, "
+                         "times --steps rounds and reports")
     args = ap.parse_args()
 
     from msrflute_amd.comm import runtime as rt_mod
@@ -116,8 +154,11 @@ def main():
     rt = rt_mod.init_runtime(backend=backend, seed=1234)
 
     config = build_config(args)
-    config["model_path"] = os.path.join("gpurun_out", "bench_models")
-    os.makedirs(config["model_path"], exist_ok=True)
+    # the engine wants a model directory; the benchmark checkpoints nothing,
+    # so a scratch one that goes away with the run keeps the tree untouched
+    # (and lets the benchmark run from a read-only checkout)
+    model_dir = tempfile.TemporaryDirectory(prefix="bench_models_")
+    config["model_path"] = model_dir.name
 
     # synthetic federated shards, cached the way the engine expects
     blob = make_femnist_blob(n_users=args.clients,
@@ -184,6 +225,15 @@ def main():
         print(json.dumps({"bench_stats_ms_per_client": per_client,
                           "clients_processed": n,
                           "ms_per_round_wall": elapsed / args.steps * 1000}))
+    if args.dump_outputs and rt.rank == 0:
+        # what a caller of run_one_round holds after the last timed round:
+        # the updated global model (replicated on every rank) and the
+        # round's per-client training losses, in sampling order
+        dump_outputs(args.dump_outputs, {
+            "global_params": arena.data.detach().float().cpu().numpy(),
+            "client_train_losses": np.asarray(server.train_loss,
+                                              dtype=np.float64),
+        })
     if rt.rank == 0:
         print(json.dumps({
             "metric": "fl_rounds_per_sec",
@@ -219,6 +269,7 @@ def main():
             },
         }))
     rt.shutdown()
+    model_dir.cleanup()
 
 
 if __name__ == "__main__":

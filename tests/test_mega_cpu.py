@@ -15,7 +15,9 @@ def _resnet_model(seed):
     with open(os.path.join(REPO, "configs/cv_resnet_fedcifar100.yaml")) as f:
         cfg = yaml.safe_load(f)
     torch.manual_seed(seed)
-    return make_model(cfg["model_config"]).double()
+    # make_model puts the model on the GPU where there is one; these are
+    # CPU-side checks (exact f64 equality), so bring it back
+    return make_model(cfg["model_config"]).double().cpu()
 
 
 def test_resnet_mega_forward_exact_in_f64():

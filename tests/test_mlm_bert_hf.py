@@ -102,7 +102,10 @@ def test_prediction_loop_single_process(hf_dir):
                            args={"tokenizer_name": hf_dir,
                                  "batch_size": 2, "max_seq_length": 16,
                                  "mlm_probability": 0.3})
-    m = _load_task_model(hf_dir)
+    # the engine moves a task model to its device (make_model); the model's
+    # _prepare puts every batch there
+    from msrflute_amd.utils import to_device
+    m = to_device(_load_task_model(hf_dir))
     out = m.prediction_loop(dl)
     assert out["predictions"].shape == out["label_ids"].shape
     assert out["predictions"].numel() > 0
@@ -132,7 +135,8 @@ dl = dl_mod.DataLoader(blob, user_idx=-1, mode="val",
                        args={"tokenizer_name": hf, "batch_size": 2,
                              "max_seq_length": 16, "mlm_probability": 0.4})
 torch.manual_seed(0)
-model = m_mod.BERT({"BERT": {"model": {"model_name_or_path": hf}}})
+from msrflute_amd.utils import to_device
+model = to_device(m_mod.BERT({"BERT": {"model": {"model_name_or_path": hf}}}))
 out = model.prediction_loop(dl, runtime=rt)
 # gathered across ranks: every rank sees the union
 n_local_tokens = int(os.environ.get("CHECK", "0"))

@@ -20,7 +20,13 @@ Design:
   (cerberus, easydict, azureml, wget) are satisfied by the minimal shims
   in tools/parity/shims/ (see each shim's docstring).
 
+* `--record-golden DIR` stores the reference run's metric series and
+  final weights; `--golden DIR` compares this engine against such a
+  record instead of running the reference, so the comparison also works
+  where no reference checkout exists (tests/test_parity_reference.py).
+
 Usage: python tools/parity/run_parity.py [--workdir DIR] [--rounds N]
+                                         [--golden DIR | --record-golden DIR]
 Writes <workdir>/PARITY_REPORT.md and exits nonzero on mismatch.
 """
 
@@ -184,11 +190,45 @@ def series(recs, key):
     return [r["value"] for r in recs if r["key"] == key]
 
 
+GOLDEN_KEYS = ("Training loss", "Test acc")
+
+
+def save_golden(golden_dir, rounds, ref_recs, ref_weights):
+    """Record what the comparison needs of a reference run: the metric
+    series and the final model weights."""
+    os.makedirs(golden_dir, exist_ok=True)
+    with open(os.path.join(golden_dir, "ref_metrics.jsonl"), "w") as f:
+        f.write(json.dumps({"key": "rounds", "value": rounds}) + "\n")
+        for r in ref_recs:
+            if r["key"] in GOLDEN_KEYS:
+                f.write(json.dumps({"key": r["key"],
+                                    "value": r["value"]}) + "\n")
+    np.savez(os.path.join(golden_dir, "ref_final_weights.npz"),
+             **{k: v.numpy() for k, v in ref_weights.items()})
+
+
+def load_golden(golden_dir, rounds):
+    recs = parse_jsonl(os.path.join(golden_dir, "ref_metrics.jsonl"))
+    recorded = series(recs, "rounds")
+    if recorded != [rounds]:
+        raise SystemExit(f"golden results were recorded for {recorded} "
+                         f"rounds, this run asks for {rounds}")
+    with np.load(os.path.join(golden_dir, "ref_final_weights.npz")) as z:
+        weights = {k: torch.from_numpy(z[k]).float() for k in z.files}
+    return recs, weights
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--workdir", default=os.path.join(REPO, "gpurun_out",
                                                       "parity"))
     ap.add_argument("--rounds", type=int, default=ROUNDS)
+    ap.add_argument("--golden", metavar="DIR", default=None,
+                    help="do not run the reference; compare this engine "
+                         "against the reference results recorded in DIR")
+    ap.add_argument("--record-golden", metavar="DIR", default=None,
+                    help="run the reference and record its results "
+                         "(metric series + final weights) into DIR")
     args = ap.parse_args()
     wd = os.path.abspath(args.workdir)
     shutil.rmtree(wd, ignore_errors=True)
@@ -200,14 +240,15 @@ def main():
     # ---- reference sandbox (symlinks; reference reads ./core/schema.py
     # and ./data relative to cwd, and we must not write /root/reference) --
     sandbox = os.path.join(wd, "ref_sandbox")
-    os.makedirs(sandbox, exist_ok=True)
-    for name in ["core", "utils", "experiments", "extensions",
-                 "e2e_trainer.py"]:
-        dst = os.path.join(sandbox, name)
-        if not os.path.exists(dst):
-            os.symlink(os.path.join(REFERENCE, name), dst)
-    write_reference_zip(os.path.join(sandbox, "data"), users, num_samples,
-                        xs, ys, xt, yt)
+    if not args.golden:
+        os.makedirs(sandbox, exist_ok=True)
+        for name in ["core", "utils", "experiments", "extensions",
+                     "e2e_trainer.py"]:
+            dst = os.path.join(sandbox, name)
+            if not os.path.exists(dst):
+                os.symlink(os.path.join(REFERENCE, name), dst)
+        write_reference_zip(os.path.join(sandbox, "data"), users,
+                            num_samples, xs, ys, xt, yt)
     our_data = os.path.join(wd, "our_data")
     write_our_blobs(our_data, users, num_samples, xs, ys, xt, yt)
 
@@ -243,13 +284,18 @@ def main():
         "MASTER_ADDR": "127.0.0.1", "HSA_ENABLE_IPC_MODE_LEGACY": "0",
     })
     env_ref.pop("RANK", None), env_ref.pop("WORLD_SIZE", None)
-    print("[parity] running REFERENCE (gloo, 2 procs)...", flush=True)
-    run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1",
-         "--nproc_per_node=2", "--master-addr", "127.0.0.1",
-         "--master-port", str(free_port()), "e2e_trainer.py",
-         "-config", ref_cfg_path, "-outputPath", ref_out,
-         "-dataPath", ".", "-task", "cv_lr_mnist", "-backend", "gloo"],
-        cwd=sandbox, env=env_ref, log_path=os.path.join(wd, "ref_run.log"))
+    if args.golden:
+        print(f"[parity] REFERENCE results recorded in {args.golden}",
+              flush=True)
+    else:
+        print("[parity] running REFERENCE (gloo, 2 procs)...", flush=True)
+        run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1",
+             "--nproc_per_node=2", "--master-addr", "127.0.0.1",
+             "--master-port", str(free_port()), "e2e_trainer.py",
+             "-config", ref_cfg_path, "-outputPath", ref_out,
+             "-dataPath", ".", "-task", "cv_lr_mnist", "-backend", "gloo"],
+            cwd=sandbox, env=env_ref,
+            log_path=os.path.join(wd, "ref_run.log"))
 
     env_ours = dict(os.environ)
     env_ours.update({"FLUTE_EXPERIMENT_NAME": "parity-run",
@@ -265,7 +311,17 @@ def main():
         cwd=REPO, env=env_ours, log_path=os.path.join(wd, "our_run.log"))
 
     # ---- compare ---------------------------------------------------------
-    ref_recs = parse_jsonl(ref_metrics)
+    if args.golden:
+        ref_recs, ref_weights = load_golden(args.golden, args.rounds)
+    else:
+        ref_recs = parse_jsonl(ref_metrics)
+        rck = torch.load(os.path.join(ref_models, "latest_model.tar"),
+                         map_location="cpu", weights_only=False)
+        ref_weights = {k: v.float() for k, v in
+                       rck["model_state_dict"].items()}
+        if args.record_golden:
+            save_golden(args.record_golden, args.rounds, ref_recs,
+                        ref_weights)
     our_recs = parse_jsonl(os.path.join(our_out, "parity-run", "log",
                                         "metrics_rank0.jsonl"))
     ref_loss = series(ref_recs, "Training loss")
@@ -306,13 +362,11 @@ def main():
         report.append("**final test accuracy diverged (or missing)**")
 
     # final checkpoint weights
-    rck = torch.load(os.path.join(ref_models, "latest_model.tar"),
-                     map_location="cpu", weights_only=False)
     ock = torch.load(os.path.join(our_models, "latest_model.tar"),
                      map_location="cpu", weights_only=False)
-    wdiff = max((rck["model_state_dict"][k].float()
+    wdiff = max((ref_weights[k]
                  - ock["model_state_dict"][k].float()).abs().max().item()
-                for k in rck["model_state_dict"])
+                for k in ref_weights)
     report.append("")
     report.append(f"final checkpoint max|w_ref - w_ours| = {wdiff:.3e} "
                   f"(tolerance 1e-3)")
