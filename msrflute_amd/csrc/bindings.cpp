@@ -8,136 +8,7 @@
 #include <c10/hip/HIPStream.h>
 #include <hip/hip_runtime.h>
 
-extern "C" {
-void launch_pseudo_grad(float*, const float*, const float*, float, long long,
-                        hipStream_t);
-void launch_axpy(float*, const float*, float, long long, hipStream_t);
-void launch_scale(float*, float, long long, hipStream_t);
-void launch_sum_sumsq(const float*, long long, double*, hipStream_t);
-void launch_sum_sumsq2(const float*, long long, double*, double*, hipStream_t);
-int sum_sumsq2_partials(long long);
-void launch_clip_apply(float*, long long, const double*, float, float, float*,
-                       hipStream_t);
-void launch_add_gaussian_noise(float*, long long, float, unsigned long long,
-                               unsigned long long, hipStream_t);
-void launch_sgd_step(float*, const float*, float*, float, const float*, float,
-                     float, float, int, int, long long, hipStream_t);
-void launch_clip_apply_stats(float*, long long, const double*, float, float,
-                             float*, hipStream_t);
-void launch_adam_step(float*, const float*, float*, float*, float*, float,
-                      float, float, float, float, float, float, int, int,
-                      long long, hipStream_t);
-void launch_adamax_step(float*, const float*, float*, float*, float, float,
-                        float, float, float, float, long long, hipStream_t);
-void launch_segmented_sqnorm(const float*, const long long*, int, double*,
-                             hipStream_t);
-void launch_quant_bin_mask(float*, long long, const float*, const float*,
-                           const float*, int, hipStream_t);
-void launch_gru_gates(const float*, const float*, const float*, float*, int,
-                      int, hipStream_t);
-}
-
-struct CnnWorkspace {
-  float *xb, *a1, *r2, *a2, *z3, *a3, *dlogits, *dz3, *da2, *dz2, *dz1;
-  float *wsl;  // split-K partial slab (B*18432 floats) — keep in sync
-               // with the definition in fused_cnn.hip
-  float *w2t, *w2rot;  // per-batch W2 fragment layouts (18432 floats each)
-  int *yb;
-  unsigned char *pidx, *m2, *m3;
-  double *red_partials, *red_acc;
-};
-
-extern "C" void launch_lstm_seq_fwd(const float*, const float*, float*,
-                                    float*, float*, int, int, int,
-                                    hipStream_t);
-extern "C" void launch_lstm_seq_bwd(const float*, const float*, const float*,
-                                    const float*, float*, int, int, int,
-                                    hipStream_t);
-extern "C" void launch_lstm_seq_fwd_b(const float*, const float*, float*,
-                                      float*, float*, int, int, int,
-                                      hipStream_t);
-extern "C" void launch_lstm_seq_bwd_b(const float*, const float*,
-                                      const float*, const float*, float*,
-                                      int, int, int, hipStream_t);
-extern "C" void launch_gru_seq_fwd(const float*, const float*, const float*,
-                                   float*, float*, float*, int, int,
-                                   hipStream_t);
-extern "C" void launch_gru_seq_bwd(const float*, const float*, const float*,
-                                   const float*, const float*, float*,
-                                   float*, int, int, hipStream_t);
-extern "C" void launch_cnn_epoch(
-    const float* shard_x, const long long* shard_y, const long long* order,
-    long long n, int bs, int C, float* params, float* grads,
-    CnnWorkspace ws, const float* lr_t, float max_norm, float p1, float p2,
-    float* stats_acc, float* loss_acc, unsigned long long seed,
-    hipStream_t s, long long row_base, int use_bf16);
-extern "C" void launch_w2_layouts(const float*, float*, float*, hipStream_t);
-extern "C" void launch_conv2_fwd_mfma(const float*, const float*,
-                                      const float*, int, float*, hipStream_t);
-extern "C" void launch_conv2_bwd_x_mfma(const float*, const float*,
-                                        const float*, int, float*,
-                                        hipStream_t);
-extern "C" void launch_conv2_bwd_w_mfma(const float*, const float*, int,
-                                        float*, float*, float*, float*,
-                                        hipStream_t);
-extern "C" void launch_fc1_fwd_mfma(const float*, const float*, const float*,
-                                    int, float, unsigned long long,
-                                    unsigned long long, float*, float*,
-                                    float*, unsigned char*, hipStream_t);
-extern "C" void launch_fc1_bwd_w_mfma(const float*, const float*, int,
-                                      float*, float*, hipStream_t);
-extern "C" void launch_fc1_bwd_x_mfma(const float*, const float*, int,
-                                      float*, hipStream_t);
-extern "C" void launch_mfma_bf16_probe(const void*, const void*, float*,
-                                       hipStream_t);
-extern "C" void launch_fc1_fwd_mfma_bf16(const float*, const float*,
-                                         const float*, int, float,
-                                         unsigned long long,
-                                         unsigned long long, float*, float*,
-                                         float*, unsigned char*, hipStream_t);
-extern "C" void launch_conv2_fwd_mfma_bf16(const float*, const float*,
-                                           const float*, int, float*,
-                                           hipStream_t);
-extern "C" void launch_conv2_bwd_x_mfma_bf16(const float*, const float*,
-                                             const float*, int, float*,
-                                             hipStream_t);
-extern "C" void launch_conv2_bwd_w_mfma_bf16(const float*, const float*, int,
-                                             float*, float*, float*,
-                                             hipStream_t);
-
-extern "C" void launch_cnn_round_mega(
-    const float* shard_x, const long long* shard_y,
-    const long long* orders_dev,
-    const long long* row_bases_dev, const long long* order_offs_dev,
-    const long long* counts_dev, const long long* counts_host,
-    const float* weights_dev, const long long* seeds_dev,
-    int K, int bs, int C,
-    const float* server_params, float* params_stack, float* grads_stack,
-    float* round_accum,
-    float* xb, float* a1, float* r2, float* a2, float* z3, float* a3,
-    float* dlogits, float* dz3, float* da2, float* dz2, float* dz1,
-    float* w2t_stack, float* w2rot_stack, float* slab,
-    int* yb, unsigned char* pidx, unsigned char* m2, unsigned char* m3,
-    double* acc2k,
-    const float* lr_t, float max_norm, float p1, float p2,
-    float* stats_out, float* loss_out, hipStream_t s, int use_bf16);
-
-extern "C" void launch_mega_clip_sgd(float*, float*, long long, int,
-                                     double*, float, const float*, float*,
-                                     hipStream_t);
-extern "C" void launch_mega_pseudo_accum(float*, const float*, const float*,
-                                         const float*, float*, long long,
-                                         int, hipStream_t);
-
-extern "C" void launch_cnn_round(
-    const float* shard_x, const long long* shard_y, const long long* orders,
-    const long long* row_bases, const long long* order_offs,
-    const long long* counts, const float* weights,
-    const unsigned long long* seeds, int K, int bs, int C,
-    const float* server_params, float* params, float* grads,
-    float* round_accum, CnnWorkspace ws, const float* lr_t, float max_norm,
-    float p1, float p2, float* stats_out, float* loss_out, hipStream_t s,
-    int use_bf16);
+#include "launchers.h"
 
 namespace {
 
@@ -301,49 +172,8 @@ void quant_bin_mask(torch::Tensor x, torch::Tensor min_t, torch::Tensor max_t,
                         thresh_t.data_ptr<float>(), (int)n_bins, cur_stream());
 }
 
-// fully-fused CNN-FEMNIST client epoch (fused_cnn.hip): one host call
-// trains a whole local epoch — fwd, bwd, clip+stats, SGD per batch —
-// bypassing autograd and hip graphs entirely.
-static CnnWorkspace slice_ws(torch::Tensor&, torch::Tensor&,
-                             torch::Tensor&, torch::Tensor&, int, int);
-
-void cnn_epoch(torch::Tensor shard_x, torch::Tensor shard_y,
-               torch::Tensor order, int64_t bs, int64_t C,
-               torch::Tensor params, torch::Tensor grads,
-               torch::Tensor work_f, torch::Tensor work_i,
-               torch::Tensor work_b, torch::Tensor work_d,
-               torch::Tensor lr_t, double max_norm, double p1, double p2,
-               torch::Tensor stats_acc, torch::Tensor loss_acc,
-               int64_t seed, bool use_bf16) {
-  check_flat(params, "params"); check_flat(grads, "grads");
-  check_flat(lr_t, "lr_t"); check_flat(stats_acc, "stats_acc");
-  check_flat(loss_acc, "loss_acc"); check_flat(work_f, "work_f");
-  TORCH_CHECK(shard_x.is_cuda() && shard_x.is_contiguous() &&
-              shard_x.scalar_type() == torch::kFloat32, "shard_x");
-  TORCH_CHECK(shard_y.is_cuda() && shard_y.is_contiguous() &&
-              shard_y.scalar_type() == torch::kInt64, "shard_y");
-  TORCH_CHECK(order.is_cuda() && order.scalar_type() == torch::kInt64,
-              "order must be int64 on device");
-  long long n = shard_y.numel();
-  TORCH_CHECK(shard_x.numel() == n * 784, "shard_x must be [n,784]");
-  TORCH_CHECK(bs >= 1 && bs <= 32, "fused CNN epoch supports batch <= 32");
-  int B = (int)bs;
-  // ONE shared slicer (slice_ws) lays out the workspace — a duplicated
-  // inline copy here once drifted from it and left ws.wsl dangling
-  CnnWorkspace ws = slice_ws(work_f, work_i, work_b, work_d, B, (int)C);
-  launch_cnn_epoch(shard_x.data_ptr<float>(),
-                   reinterpret_cast<const long long*>(
-                       shard_y.data_ptr<int64_t>()),
-                   reinterpret_cast<const long long*>(
-                       order.data_ptr<int64_t>()),
-                   n, B, (int)C,
-                   params.data_ptr<float>(), grads.data_ptr<float>(), ws,
-                   lr_t.data_ptr<float>(), (float)max_norm, (float)p1,
-                   (float)p2, stats_acc.data_ptr<float>(),
-                   loss_acc.data_ptr<float>(), (unsigned long long)seed,
-                   cur_stream(), 0, use_bf16 ? 1 : 0);
-}
-
+// the ONE slicer that lays the per-client CNN workspace out inside the
+// caller's buffers (cnn_epoch and cnn_round share it)
 static CnnWorkspace slice_ws(torch::Tensor& work_f, torch::Tensor& work_i,
                              torch::Tensor& work_b, torch::Tensor& work_d,
                              int B, int C) {
@@ -377,6 +207,44 @@ static CnnWorkspace slice_ws(torch::Tensor& work_f, torch::Tensor& work_i,
   ws.red_partials = work_d.data_ptr<double>();
   ws.red_acc = work_d.data_ptr<double>() + work_d.numel() - 2;
   return ws;
+}
+
+// fully-fused CNN-FEMNIST client epoch (fused_cnn.hip): one host call
+// trains a whole local epoch — fwd, bwd, clip+stats, SGD per batch —
+// bypassing autograd and hip graphs entirely.
+void cnn_epoch(torch::Tensor shard_x, torch::Tensor shard_y,
+               torch::Tensor order, int64_t bs, int64_t C,
+               torch::Tensor params, torch::Tensor grads,
+               torch::Tensor work_f, torch::Tensor work_i,
+               torch::Tensor work_b, torch::Tensor work_d,
+               torch::Tensor lr_t, double max_norm, double p1, double p2,
+               torch::Tensor stats_acc, torch::Tensor loss_acc,
+               int64_t seed, bool use_bf16) {
+  check_flat(params, "params"); check_flat(grads, "grads");
+  check_flat(lr_t, "lr_t"); check_flat(stats_acc, "stats_acc");
+  check_flat(loss_acc, "loss_acc"); check_flat(work_f, "work_f");
+  TORCH_CHECK(shard_x.is_cuda() && shard_x.is_contiguous() &&
+              shard_x.scalar_type() == torch::kFloat32, "shard_x");
+  TORCH_CHECK(shard_y.is_cuda() && shard_y.is_contiguous() &&
+              shard_y.scalar_type() == torch::kInt64, "shard_y");
+  TORCH_CHECK(order.is_cuda() && order.scalar_type() == torch::kInt64,
+              "order must be int64 on device");
+  long long n = shard_y.numel();
+  TORCH_CHECK(shard_x.numel() == n * 784, "shard_x must be [n,784]");
+  TORCH_CHECK(bs >= 1 && bs <= 32, "fused CNN epoch supports batch <= 32");
+  int B = (int)bs;
+  CnnWorkspace ws = slice_ws(work_f, work_i, work_b, work_d, B, (int)C);
+  launch_cnn_epoch(shard_x.data_ptr<float>(),
+                   reinterpret_cast<const long long*>(
+                       shard_y.data_ptr<int64_t>()),
+                   reinterpret_cast<const long long*>(
+                       order.data_ptr<int64_t>()),
+                   n, B, (int)C,
+                   params.data_ptr<float>(), grads.data_ptr<float>(), ws,
+                   lr_t.data_ptr<float>(), (float)max_norm, (float)p1,
+                   (float)p2, stats_acc.data_ptr<float>(),
+                   loss_acc.data_ptr<float>(), (unsigned long long)seed,
+                   cur_stream(), 0, use_bf16 ? 1 : 0);
 }
 
 // whole-round driver: K clients in ONE host call (copy-in, fused epoch,
@@ -588,21 +456,44 @@ torch::Tensor gru_gates(torch::Tensor g_i, torch::Tensor g_h,
 }  // namespace
 
 // ---------------------------------------------------------------------------
-// per-kernel MFMA debug entries (numerics tests vs torch references;
-// the epoch driver calls the same kernels internally)
+// per-kernel MFMA debug entries (numerics tests vs torch references; the
+// drivers launch the same kernels).  Operands may be K-stacked: B is the
+// total row count, client k owns rows [k*B/K, (k+1)*B/K) and the k-th
+// block of every weight / bias / gradient tensor.  K is inferred from the
+// weight length where a weight is passed and given explicitly where only
+// gradients come out.
 // ---------------------------------------------------------------------------
+static int rows_per_client(int64_t B, int64_t K) {
+  TORCH_CHECK(K >= 1 && B >= K && B % K == 0, "B rows must split over K");
+  return (int)(B / K);
+}
+
+// the fc1 GEMMs mask ONE 32-row tile per client
+static int fc1_rows_per_client(int64_t B, int64_t K) {
+  int bs = rows_per_client(B, K);
+  TORCH_CHECK(bs <= 32, "fc1 kernels take at most 32 rows per client");
+  return bs;
+}
+
+static int stack_len(const torch::Tensor& w, int64_t per, const char* name) {
+  TORCH_CHECK(w.numel() > 0 && w.numel() % per == 0, name,
+              " must hold K blocks of ", per);
+  return (int)(w.numel() / per);
+}
+
 torch::Tensor dbg_conv2_fwd_mfma(torch::Tensor a1, torch::Tensor w2,
                                  torch::Tensor b2, int64_t B) {
   check_flat(a1, "a1"); check_flat(w2, "w2"); check_flat(b2, "b2");
-  TORCH_CHECK(a1.numel() >= B * 21632 && w2.numel() == 18432 &&
-              b2.numel() == 64);
+  int K = stack_len(w2, 18432, "w2");
+  int bs = rows_per_client(B, K);
+  TORCH_CHECK(a1.numel() >= B * 21632 && b2.numel() == K * 64);
   auto r2 = torch::empty({B * 36864}, a1.options());
-  auto w2t = torch::empty({18432}, a1.options());
-  auto w2rot = torch::empty({18432}, a1.options());
-  launch_w2_layouts(w2.data_ptr<float>(), w2t.data_ptr<float>(),
+  auto w2t = torch::empty_like(w2);
+  auto w2rot = torch::empty_like(w2);
+  launch_w2_layouts(w2.data_ptr<float>(), K, w2t.data_ptr<float>(),
                     w2rot.data_ptr<float>(), cur_stream());
   launch_conv2_fwd_mfma(a1.data_ptr<float>(), w2t.data_ptr<float>(),
-                        b2.data_ptr<float>(), (int)B, r2.data_ptr<float>(),
+                        b2.data_ptr<float>(), bs, K, r2.data_ptr<float>(),
                         cur_stream());
   return r2;
 }
@@ -610,32 +501,44 @@ torch::Tensor dbg_conv2_fwd_mfma(torch::Tensor a1, torch::Tensor w2,
 torch::Tensor dbg_conv2_fwd_mfma_bf16(torch::Tensor a1, torch::Tensor w2,
                                       torch::Tensor b2, int64_t B) {
   check_flat(a1, "a1"); check_flat(w2, "w2"); check_flat(b2, "b2");
+  int K = stack_len(w2, 18432, "w2");
+  int bs = rows_per_client(B, K);
+  TORCH_CHECK(a1.numel() >= B * 21632 && b2.numel() == K * 64);
+  // the kernel reads w2 and b2 through one stack pointer
+  auto w2b2 = torch::cat({w2.view({K, 18432}), b2.view({K, 64})}, 1)
+                  .contiguous();
   auto r2 = torch::empty({B * 36864}, a1.options());
-  launch_conv2_fwd_mfma_bf16(a1.data_ptr<float>(), w2.data_ptr<float>(),
-                             b2.data_ptr<float>(), (int)B,
-                             r2.data_ptr<float>(), cur_stream());
+  launch_conv2_fwd_mfma_bf16(a1.data_ptr<float>(), w2b2.data_ptr<float>(),
+                             bs, K, r2.data_ptr<float>(), cur_stream());
   return r2;
 }
 
 torch::Tensor dbg_conv2_bwd_x_mfma_bf16(torch::Tensor dz2, torch::Tensor w2,
                                         torch::Tensor a1, int64_t B) {
   check_flat(dz2, "dz2"); check_flat(w2, "w2"); check_flat(a1, "a1");
+  int K = stack_len(w2, 18432, "w2");
+  int bs = rows_per_client(B, K);
+  TORCH_CHECK(dz2.numel() >= B * 36864 && a1.numel() >= B * 21632);
   auto dz1 = torch::empty({B * 21632}, dz2.options());
+  auto w2rotbf = torch::empty_like(w2);  // holds K*18432 bf16
   launch_conv2_bwd_x_mfma_bf16(dz2.data_ptr<float>(), w2.data_ptr<float>(),
-                               a1.data_ptr<float>(), (int)B,
+                               a1.data_ptr<float>(), bs, K,
+                               w2rotbf.data_ptr<float>(),
                                dz1.data_ptr<float>(), cur_stream());
   return dz1;
 }
 
 std::vector<torch::Tensor> dbg_conv2_bwd_w_mfma_bf16(torch::Tensor dz2,
                                                      torch::Tensor a1,
-                                                     int64_t B) {
+                                                     int64_t B, int64_t K) {
   check_flat(dz2, "dz2"); check_flat(a1, "a1");
+  int bs = rows_per_client(B, K);
+  TORCH_CHECK(dz2.numel() >= B * 36864 && a1.numel() >= B * 21632);
   auto slab = torch::empty({B * 18432}, dz2.options());
-  auto dw2 = torch::empty({18432}, dz2.options());
-  auto db2 = torch::empty({64}, dz2.options());
+  auto dw2 = torch::empty({K * 18432}, dz2.options());
+  auto db2 = torch::empty({K * 64}, dz2.options());
   launch_conv2_bwd_w_mfma_bf16(dz2.data_ptr<float>(), a1.data_ptr<float>(),
-                               (int)B, slab.data_ptr<float>(),
+                               bs, (int)K, slab.data_ptr<float>(),
                                dw2.data_ptr<float>(), db2.data_ptr<float>(),
                                cur_stream());
   return {dw2, db2};
@@ -647,12 +550,15 @@ std::vector<torch::Tensor> dbg_fc1_fwd_mfma_bf16(torch::Tensor a2,
                                                  double p2, int64_t seed,
                                                  int64_t offset) {
   check_flat(a2, "a2"); check_flat(w3, "w3"); check_flat(b3, "b3");
+  int K = stack_len(w3, 128 * 9216, "w3");
+  int bs = fc1_rows_per_client(B, K);
+  TORCH_CHECK(a2.numel() >= B * 9216 && b3.numel() == K * 128);
   auto slab = torch::empty({36 * B * 128}, a2.options());
   auto z3 = torch::empty({B * 128}, a2.options());
   auto a3 = torch::empty({B * 128}, a2.options());
   auto m3 = torch::empty({B * 128}, a2.options().dtype(torch::kUInt8));
   launch_fc1_fwd_mfma_bf16(a2.data_ptr<float>(), w3.data_ptr<float>(),
-                           b3.data_ptr<float>(), (int)B, (float)p2,
+                           b3.data_ptr<float>(), bs, K, (float)p2,
                            (unsigned long long)seed,
                            (unsigned long long)offset,
                            slab.data_ptr<float>(), z3.data_ptr<float>(),
@@ -664,27 +570,32 @@ std::vector<torch::Tensor> dbg_fc1_fwd_mfma_bf16(torch::Tensor a2,
 torch::Tensor dbg_conv2_bwd_x_mfma(torch::Tensor dz2, torch::Tensor w2,
                                    torch::Tensor a1, int64_t B) {
   check_flat(dz2, "dz2"); check_flat(w2, "w2"); check_flat(a1, "a1");
+  int K = stack_len(w2, 18432, "w2");
+  int bs = rows_per_client(B, K);
   TORCH_CHECK(dz2.numel() >= B * 36864 && a1.numel() >= B * 21632);
   auto dz1 = torch::empty({B * 21632}, dz2.options());
-  auto w2t = torch::empty({18432}, dz2.options());
-  auto w2rot = torch::empty({18432}, dz2.options());
-  launch_w2_layouts(w2.data_ptr<float>(), w2t.data_ptr<float>(),
+  auto w2t = torch::empty_like(w2);
+  auto w2rot = torch::empty_like(w2);
+  launch_w2_layouts(w2.data_ptr<float>(), K, w2t.data_ptr<float>(),
                     w2rot.data_ptr<float>(), cur_stream());
   launch_conv2_bwd_x_mfma(dz2.data_ptr<float>(), w2rot.data_ptr<float>(),
-                          a1.data_ptr<float>(), (int)B,
+                          a1.data_ptr<float>(), bs, K,
                           dz1.data_ptr<float>(), cur_stream());
   return dz1;
 }
 
 std::vector<torch::Tensor> dbg_conv2_bwd_w_mfma(torch::Tensor dz2,
-                                                torch::Tensor a1, int64_t B) {
+                                                torch::Tensor a1, int64_t B,
+                                                int64_t K) {
   check_flat(dz2, "dz2"); check_flat(a1, "a1");
+  int bs = rows_per_client(B, K);
+  TORCH_CHECK(dz2.numel() >= B * 36864 && a1.numel() >= B * 21632);
   auto slab = torch::empty({B * 18432}, dz2.options());
   auto dz2t = torch::empty({B * 36864}, dz2.options());
-  auto dw2 = torch::empty({18432}, dz2.options());
-  auto db2 = torch::empty({64}, dz2.options());
+  auto dw2 = torch::empty({K * 18432}, dz2.options());
+  auto db2 = torch::empty({K * 64}, dz2.options());
   launch_conv2_bwd_w_mfma(dz2.data_ptr<float>(), a1.data_ptr<float>(),
-                          (int)B, dz2t.data_ptr<float>(),
+                          bs, (int)K, dz2t.data_ptr<float>(),
                           slab.data_ptr<float>(),
                           dw2.data_ptr<float>(), db2.data_ptr<float>(),
                           cur_stream());
@@ -697,13 +608,15 @@ std::vector<torch::Tensor> dbg_fc1_fwd_mfma(torch::Tensor a2,
                                             double p2, int64_t seed,
                                             int64_t offset) {
   check_flat(a2, "a2"); check_flat(w3, "w3"); check_flat(b3, "b3");
-  TORCH_CHECK(a2.numel() >= B * 9216 && w3.numel() == 128 * 9216);
+  int K = stack_len(w3, 128 * 9216, "w3");
+  int bs = fc1_rows_per_client(B, K);
+  TORCH_CHECK(a2.numel() >= B * 9216 && b3.numel() == K * 128);
   auto slab = torch::empty({64 * B * 128}, a2.options());
   auto z3 = torch::empty({B * 128}, a2.options());
   auto a3 = torch::empty({B * 128}, a2.options());
   auto m3 = torch::empty({B * 128}, a2.options().dtype(torch::kUInt8));
   launch_fc1_fwd_mfma(a2.data_ptr<float>(), w3.data_ptr<float>(),
-                      b3.data_ptr<float>(), (int)B, (float)p2,
+                      b3.data_ptr<float>(), bs, K, (float)p2,
                       (unsigned long long)seed, (unsigned long long)offset,
                       slab.data_ptr<float>(), z3.data_ptr<float>(),
                       a3.data_ptr<float>(), m3.data_ptr<unsigned char>(),
@@ -712,12 +625,15 @@ std::vector<torch::Tensor> dbg_fc1_fwd_mfma(torch::Tensor a2,
 }
 
 std::vector<torch::Tensor> dbg_fc1_bwd_w_mfma(torch::Tensor dz3,
-                                              torch::Tensor a2, int64_t B) {
+                                              torch::Tensor a2, int64_t B,
+                                              int64_t K) {
   check_flat(dz3, "dz3"); check_flat(a2, "a2");
-  auto dw3 = torch::empty({128 * 9216}, dz3.options());
-  auto db3 = torch::empty({128}, dz3.options());
-  launch_fc1_bwd_w_mfma(dz3.data_ptr<float>(), a2.data_ptr<float>(), (int)B,
-                        dw3.data_ptr<float>(), db3.data_ptr<float>(),
+  int bs = fc1_rows_per_client(B, K);
+  TORCH_CHECK(dz3.numel() >= B * 128 && a2.numel() >= B * 9216);
+  auto dw3 = torch::empty({K * 128 * 9216}, dz3.options());
+  auto db3 = torch::empty({K * 128}, dz3.options());
+  launch_fc1_bwd_w_mfma(dz3.data_ptr<float>(), a2.data_ptr<float>(), bs,
+                        (int)K, dw3.data_ptr<float>(), db3.data_ptr<float>(),
                         cur_stream());
   return {dw3, db3};
 }
@@ -725,8 +641,11 @@ std::vector<torch::Tensor> dbg_fc1_bwd_w_mfma(torch::Tensor dz3,
 torch::Tensor dbg_fc1_bwd_x_mfma(torch::Tensor dz3, torch::Tensor w3,
                                  int64_t B) {
   check_flat(dz3, "dz3"); check_flat(w3, "w3");
+  int K = stack_len(w3, 128 * 9216, "w3");
+  int bs = fc1_rows_per_client(B, K);
+  TORCH_CHECK(dz3.numel() >= B * 128);
   auto da2 = torch::empty({B * 9216}, dz3.options());
-  launch_fc1_bwd_x_mfma(dz3.data_ptr<float>(), w3.data_ptr<float>(), (int)B,
+  launch_fc1_bwd_x_mfma(dz3.data_ptr<float>(), w3.data_ptr<float>(), bs, K,
                         da2.data_ptr<float>(), cur_stream());
   return da2;
 }
@@ -744,7 +663,7 @@ torch::Tensor dbg_mfma_bf16_probe(torch::Tensor A, torch::Tensor B) {
 }
 
 // MEGA round: every sampled client of the round in ONE launch set per
-// batch-step (fused_cnn_mega.hip).  Caller provides the per-client
+// batch-step (fused_cnn.hip).  Caller provides the per-client
 // metadata both on device (kernel use) and host (max_batches), the
 // K*P parameter/gradient stacks and a float workspace sliced here.
 void cnn_round_mega(torch::Tensor shard_x, torch::Tensor shard_y,
@@ -890,13 +809,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("dbg_mfma_bf16_probe", &dbg_mfma_bf16_probe);
   m.def("dbg_conv2_fwd_mfma_bf16", &dbg_conv2_fwd_mfma_bf16);
   m.def("dbg_conv2_bwd_x_mfma_bf16", &dbg_conv2_bwd_x_mfma_bf16);
-  m.def("dbg_conv2_bwd_w_mfma_bf16", &dbg_conv2_bwd_w_mfma_bf16);
+  m.def("dbg_conv2_bwd_w_mfma_bf16", &dbg_conv2_bwd_w_mfma_bf16,
+        py::arg("dz2"), py::arg("a1"), py::arg("B"), py::arg("K") = 1);
   m.def("dbg_fc1_fwd_mfma_bf16", &dbg_fc1_fwd_mfma_bf16);
   m.def("dbg_conv2_fwd_mfma", &dbg_conv2_fwd_mfma);
   m.def("dbg_conv2_bwd_x_mfma", &dbg_conv2_bwd_x_mfma);
-  m.def("dbg_conv2_bwd_w_mfma", &dbg_conv2_bwd_w_mfma);
+  m.def("dbg_conv2_bwd_w_mfma", &dbg_conv2_bwd_w_mfma,
+        py::arg("dz2"), py::arg("a1"), py::arg("B"), py::arg("K") = 1);
   m.def("dbg_fc1_fwd_mfma", &dbg_fc1_fwd_mfma);
-  m.def("dbg_fc1_bwd_w_mfma", &dbg_fc1_bwd_w_mfma);
+  m.def("dbg_fc1_bwd_w_mfma", &dbg_fc1_bwd_w_mfma,
+        py::arg("dz3"), py::arg("a2"), py::arg("B"), py::arg("K") = 1);
   m.def("dbg_fc1_bwd_x_mfma", &dbg_fc1_bwd_x_mfma);
   m.doc() = "msrflute_amd gfx950 flat-arena kernels";
   m.def("pseudo_grad", &pseudo_grad);

@@ -22,6 +22,8 @@
 #include <hip/hip_runtime.h>
 #include <hiprand/hiprand_kernel.h>
 
+#include "launchers.h"
+
 #define WAVE 64
 #define BLOCK 256
 #define MAX_BLOCKS 2048

@@ -1,65 +1,84 @@
-// Fully-fused CNN-FEMNIST client step for gfx950 (BASELINE north star:
-// "Client.process_round() local-SGD ... as hand-written CDNA4 HIP
-// kernels").  The flagship benchmark model (reference
-// experiments/cv_cnn_femnist/model.py: conv1 1->32 3x3, relu, conv2
-// 32->64 3x3, relu, maxpool2, dropout .25, fc1 9216->128, relu,
-// dropout .5, fc2 128->C, CE) trained WITHOUT torch autograd: forward,
-// backward, clip+stats and the SGD step are ~17 kernel launches per
-// batch driven by ONE host call per epoch (launch_cnn_epoch).
+// Fully-fused CNN-FEMNIST client step for gfx950.  The flagship
+// benchmark model (experiments/cv_cnn_femnist/model.py: conv1 1->32 3x3,
+// relu, conv2 32->64 3x3, relu, maxpool2, dropout .25, fc1 9216->128,
+// relu, dropout .5, fc2 128->C, CE) trained WITHOUT torch autograd:
+// forward, backward, clip+stats and the SGD step are ~20 kernel launches
+// per batch driven by one host call.  Gradients are written (not
+// accumulated) straight into the flat arena at the parameters' fixed
+// offsets, so no zero_grad is needed either.  Shapes are the task's
+// (28x28 in, spatial 26/24/12 fixed); batch size and class count C are
+// runtime args.
 //
-// Why: hipGraphLaunch costs ~4.6us/node on this stack, so the ~230-node
-// autograd capture costs ~1.07 ms host per client epoch (PERF.md).  This
-// path is ~85 raw launches (~2us each) per epoch and owns its numerics:
-// gradients are written (not accumulated) straight into the flat arena
-// at the parameters' fixed offsets, so no zero_grad is needed either.
+// ONE kernel set serves both drivers.  Every kernel is written for the
+// cross-client mega round (launch_cnn_round_mega): ONE launch set per
+// batch-step trains ALL K sampled clients, the super-batch dimension is
+// G = K*bs rows (row g belongs to client k = g/bs), every kernel takes
+// per-client parameter/gradient stacks (params_stack[k*P ..]), and grids
+// scale by K — conv2 fwd is K*bs*9 = 1800 blocks at the benchmark shape,
+// where a per-client grid (180 blocks) underfills the 256-CU chip.  The
+// per-client epoch (launch_cnn_epoch) launches the same kernels at K = 1
+// with bs := the batch's actual row count and the client's own arena as
+// the stack.  Only the four ops that read per-client metadata (gather,
+// pool dropout, fc1 reduce, loss) have two thin __global__ wrappers
+// around one __device__ body: the mega wrapper reads seeds[k]/counts[k]
+// from device arrays, the per-client one takes them as launch arguments
+// so that path uploads nothing.
 //
-// Shapes are the task's (28x28 in, spatial 26/24/12 fixed); batch B and
-// class count C are runtime args.  Dropout uses Philox keyed by
-// (seed, batch_index) — deterministic per client epoch.
+// Ragged handling is free of masks in the backward chain: the gather
+// zero-fills inactive rows (b >= B_k(t)) and writes yb = -1, the loss
+// kernel zeroes those rows' dlogits, and every weight gradient is then
+// exactly the per-client value (zero rows contribute nothing).  Clients
+// whose epochs ended (t >= ceil(count/bs)) naturally produce zero
+// gradients and their SGD step no-ops.  Dropout Philox streams use
+// CLIENT-LOCAL indices keyed by (seed, batch index), so masks are
+// bit-identical between the two drivers and deterministic per client
+// epoch.
 
 #include <hip/hip_runtime.h>
 #include <hiprand/hiprand_kernel.h>
 
+#include <cstdio>
+#include <cstdlib>
+
+#include "launchers.h"
+
 #define FBLK 256
 
-// arena offsets (fp32 indices) for C classes
-struct CnnOffsets {
-  long long w1, b1, w2, b2, w3, b3, w4, b4, total;
-};
+// gfx950's f32-input MFMA (v_mfma_f32_16x16x4_f32) is EXACT f32 — a
+// k-ordered fmaf chain at the full f32 rate — so the f32 GEMM kernels
+// keep fp32 numerics while moving the matrix work onto the matrix pipe.
+// Fragment maps: A[i=l&15][k=l>>4], B[k=l>>4][j=l&15] one f32 VGPR each;
+// D[row=(l>>4)*4+r][col=l&15], 4 f32 per lane.
+typedef __attribute__((ext_vector_type(4))) float f32x4;
 
-static CnnOffsets cnn_offsets(int C) {
-  CnnOffsets o;
-  o.w1 = 0;               // [32,1,3,3]
-  o.b1 = o.w1 + 288;      // [32]
-  o.w2 = o.b1 + 32;       // [64,32,3,3]
-  o.b2 = o.w2 + 18432;    // [64]
-  o.w3 = o.b2 + 64;       // [128,9216]
-  o.b3 = o.w3 + 1179648;  // [128]
-  o.w4 = o.b3 + 128;      // [C,128]
-  o.b4 = o.w4 + (long long)C * 128;  // [C]
-  o.total = o.b4 + C;
-  return o;
+#define MC2F_LD 585  /* padded f32 LDS row stride (585 %% 32 = 9, odd ->
+                        conflict-free 16-lane fragment groups) */
+
+// per-row helpers: g in [0, K*bs), k = g / bs, b = g % bs
+__device__ __forceinline__ int mega_Bk(const long long* counts, int k,
+                                       int t, int bs) {
+  long long rem = counts[k] - (long long)t * bs;
+  return rem <= 0 ? 0 : (rem < bs ? (int)rem : bs);
 }
 
-// ---------------------------------------------------------------------------
-// gather a shuffled batch from the device-resident shard
-// ---------------------------------------------------------------------------
-__global__ void k_gather_batch(const float* __restrict__ shard_x,
-                               const long long* __restrict__ shard_y,
-                               const long long* __restrict__ order,
-                               long long start, long long row_base, int B,
-                               float* __restrict__ xb,
-                               int* __restrict__ yb) {
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < B * 784;
-       i += gridDim.x * blockDim.x) {
-    int b = i / 784, j = i % 784;
-    long long src = row_base + order[start + b];
-    xb[i] = shard_x[src * 784 + j];
-    if (j == 0) yb[b] = (int)shard_y[src];
-  }
+__global__ void k_copy_stack(float* __restrict__ dst,
+                             const float* __restrict__ src, long long P,
+                             int K) {
+  long long total = (long long)K * P;
+  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+       i < total; i += (long long)gridDim.x * blockDim.x)
+    dst[i] = src[i % P];
 }
 
-// grad = (w_server - w_trained) * weight  (client pseudo-gradient, K1+K2)
+// per-client round plumbing (launch_cnn_round): copy-in, weighted
+// pseudo-gradient grad = (w_server - w_trained) * weight, accumulate
+__global__ void k_copy(float* __restrict__ dst, const float* __restrict__ src,
+                       long long n) {
+  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n;
+       i += (long long)gridDim.x * blockDim.x)
+    dst[i] = src[i];
+}
+
 __global__ void k_cnn_pseudo_grad(float* __restrict__ g,
                                   const float* __restrict__ ws,
                                   const float* __restrict__ wt, float weight,
@@ -76,26 +95,71 @@ __global__ void k_cnn_axpy(float* __restrict__ y, const float* __restrict__ x,
     y[i] += x[i];
 }
 
-__global__ void k_copy(float* __restrict__ dst, const float* __restrict__ src,
-                       long long n) {
-  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n;
-       i += (long long)gridDim.x * blockDim.x)
-    dst[i] = src[i];
+// ---------------------------------------------------------------------------
+// gather a shuffled batch from the device-resident shard: element j of
+// batch row g comes from shard row src
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ void gather_elem(
+    const float* __restrict__ shard_x, const long long* __restrict__ shard_y,
+    long long src, int j, long long i, long long g,
+    float* __restrict__ xb, int* __restrict__ yb) {
+  xb[i] = shard_x[src * 784 + j];
+  if (j == 0) yb[g] = (int)shard_y[src];
 }
 
-// ---------------------------------------------------------------------------
-// forward
-// ---------------------------------------------------------------------------
-// a1[b,co,y,x] = relu(b1 + sum_{kh,kw} w1[co,kh,kw] * x[b, y+kh, x+kw])
-__global__ void k_conv1_fwd(const float* __restrict__ x,
-                            const float* __restrict__ w1,
-                            const float* __restrict__ b1, int B,
-                            float* __restrict__ a1) {
-  int total = B * 32 * 26 * 26;
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total;
+__global__ void k_gather_batch(const float* __restrict__ shard_x,
+                               const long long* __restrict__ shard_y,
+                               const long long* __restrict__ order,
+                               long long start, long long row_base, int B,
+                               float* __restrict__ xb,
+                               int* __restrict__ yb) {
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < B * 784;
        i += gridDim.x * blockDim.x) {
-    int xx = i % 26, yy = (i / 26) % 26, co = (i / 676) % 32, b = i / 21632;
-    const float* xp = x + b * 784 + yy * 28 + xx;
+    int b = i / 784, j = i % 784;
+    gather_elem(shard_x, shard_y, row_base + order[start + b], j, i, b,
+                xb, yb);
+  }
+}
+
+__global__ void k_gather_mb(const float* __restrict__ shard_x,
+                            const long long* __restrict__ shard_y,
+                            const long long* __restrict__ orders,
+                            const long long* __restrict__ row_bases,
+                            const long long* __restrict__ order_offs,
+                            const long long* __restrict__ counts,
+                            int t, int bs, int K,
+                            float* __restrict__ xb, int* __restrict__ yb) {
+  int G = K * bs;
+  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+       i < (long long)G * 784; i += (long long)gridDim.x * blockDim.x) {
+    int g = (int)(i / 784), j = (int)(i % 784);
+    int k = g / bs, b = g % bs;
+    int Bk = mega_Bk(counts, k, t, bs);
+    if (b < Bk) {
+      long long src = row_bases[k]
+          + orders[order_offs[k] + (long long)t * bs + b];
+      gather_elem(shard_x, shard_y, src, j, i, g, xb, yb);
+    } else {
+      xb[i] = 0.f;
+      if (j == 0) yb[g] = -1;
+    }
+  }
+}
+
+__global__ void k_conv1_fwd_mb(const float* __restrict__ x,
+                               const float* __restrict__ params, long long P,
+                               long long ow1, long long ob1, int bs, int K,
+                               float* __restrict__ a1) {
+  long long total = (long long)K * bs * 21632;
+  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+       i < total; i += (long long)gridDim.x * blockDim.x) {
+    int xx = (int)(i % 26), yy = (int)((i / 26) % 26);
+    int co = (int)((i / 676) % 32);
+    long long g = i / 21632;
+    int k = (int)(g / bs);
+    const float* w1 = params + (long long)k * P + ow1;
+    const float* b1 = params + (long long)k * P + ob1;
+    const float* xp = x + g * 784 + yy * 28 + xx;
     const float* wp = w1 + co * 9;
     float acc = b1[co];
     #pragma unroll
@@ -107,468 +171,54 @@ __global__ void k_conv1_fwd(const float* __restrict__ x,
   }
 }
 
-// r2[b,co,y,x] = relu(b2 + sum_ci sum_k w2[co,ci,k]*a1[b,ci,y+kh,x+kw])
-// One block per (b, group of 8 co); a1's 32 input channels are staged
-// through LDS in two 16-channel tiles (42.25 KB) and reused by all 8
-// output channels — 8x less LDS-staging traffic than one-co-per-block.
-// W2 taps for the tile live in registers (8 co x 9 = 72 floats/thread is
-// too many, so taps reload per ci from L1 — W2 is 72 KB, L2-resident).
-#define CONV2_COG 8
-__global__ void k_conv2_fwd(const float* __restrict__ a1,
-                            const float* __restrict__ w2,
-                            const float* __restrict__ b2, int B,
-                            float* __restrict__ r2) {
-  __shared__ float lds[16 * 676];
-  int b = blockIdx.x / (64 / CONV2_COG);
-  int co0 = (blockIdx.x % (64 / CONV2_COG)) * CONV2_COG;
-  float acc[3][CONV2_COG];
-  #pragma unroll
-  for (int r = 0; r < 3; ++r)
-    #pragma unroll
-    for (int g = 0; g < CONV2_COG; ++g) acc[r][g] = b2[co0 + g];
-  for (int half = 0; half < 2; ++half) {
-    const float* src = a1 + ((long long)b * 32 + half * 16) * 676;
-    __syncthreads();
-    for (int i = threadIdx.x; i < 16 * 676; i += blockDim.x)
-      lds[i] = src[i];
-    __syncthreads();
-    #pragma unroll
-    for (int r = 0; r < 3; ++r) {
-      int o = threadIdx.x + r * FBLK;
-      if (o >= 576) continue;
-      int xx = o % 24, yy = o / 24;
-      for (int ci = 0; ci < 16; ++ci) {
-        const float* ap = lds + ci * 676 + yy * 26 + xx;
-        float a[9];
-        #pragma unroll
-        for (int kh = 0; kh < 3; ++kh)
-          #pragma unroll
-          for (int kw = 0; kw < 3; ++kw)
-            a[kh * 3 + kw] = ap[kh * 26 + kw];
-        #pragma unroll
-        for (int g = 0; g < CONV2_COG; ++g) {
-          const float* wq = w2 + ((long long)(co0 + g) * 32
-                                  + half * 16 + ci) * 9;
-          float s = acc[r][g];
-          #pragma unroll
-          for (int k = 0; k < 9; ++k) s = fmaf(wq[k], a[k], s);
-          acc[r][g] = s;
-        }
-      }
-    }
-  }
-  #pragma unroll
-  for (int r = 0; r < 3; ++r) {
-    int o = threadIdx.x + r * FBLK;
-    if (o < 576)
-      #pragma unroll
-      for (int g = 0; g < CONV2_COG; ++g) {
-        float v = acc[r][g];
-        r2[((long long)b * 64 + co0 + g) * 576 + o] = v > 0.f ? v : 0.f;
-      }
-  }
-}
-
-// maxpool 2x2 + dropout(p1): a2 = keep ? max/(1-p1) : 0; save argmax+mask
-__global__ void k_pool_drop_fwd(const float* __restrict__ r2, int B,
-                                float p1, unsigned long long seed,
-                                unsigned long long offset,
-                                float* __restrict__ a2,
-                                unsigned char* __restrict__ pidx,
-                                unsigned char* __restrict__ m2) {
-  int total = B * 64 * 144;
-  float inv_keep = (p1 < 1.f) ? 1.f / (1.f - p1) : 0.f;
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total;
-       i += gridDim.x * blockDim.x) {
-    int px = i % 12, py = (i / 12) % 12, c = (i / 144) % 64, b = i / 9216;
-    const float* base = r2 + (((long long)b * 64 + c) * 24 + 2 * py) * 24 + 2 * px;
-    float v0 = base[0], v1 = base[1], v2 = base[24], v3 = base[25];
-    float m = v0; int idx = 0;
-    if (v1 > m) { m = v1; idx = 1; }
-    if (v2 > m) { m = v2; idx = 2; }
-    if (v3 > m) { m = v3; idx = 3; }
-    unsigned char keep = 1;
-    if (p1 > 0.f) {
-      // one Philox draw covers 4 cells (init is ~10 rounds — the cost)
-      hiprandStatePhilox4_32_10_t st;
-      hiprand_init(seed, (unsigned long long)(i >> 2), offset, &st);
-      float4 u = hiprand_uniform4(&st);
-      float uu = (i & 3) == 0 ? u.x : (i & 3) == 1 ? u.y
-                 : (i & 3) == 2 ? u.z : u.w;
-      keep = uu >= p1;
-    }
-    pidx[i] = (unsigned char)idx;
-    m2[i] = keep;
-    a2[i] = keep ? m * inv_keep : 0.f;
-  }
-}
-
-// z3 = W3 @ a2flat + b3 ; a3 = dropout(relu(z3), p2)
-// one block per (b, j): 256-thread coalesced dot of length 9216.  (A
-// one-block-per-j variant amortizing W3 reads across B measured 3x
-// slower: the per-b a2 reads stride 9216 and kill coalescing; here both
-// streams are contiguous and L2 absorbs the W3 re-reads.)
-__global__ void k_fc1_fwd(const float* __restrict__ a2,
-                          const float* __restrict__ w3,
-                          const float* __restrict__ b3, int B, float p2,
-                          unsigned long long seed, unsigned long long offset,
-                          float* __restrict__ z3, float* __restrict__ a3,
-                          unsigned char* __restrict__ m3) {
-  int b = blockIdx.x / 128, j = blockIdx.x % 128;
-  const float* ap = a2 + (long long)b * 9216;
-  const float* wp = w3 + (long long)j * 9216;
-  float s = 0.f;
-  for (int k = threadIdx.x; k < 9216; k += blockDim.x)
-    s = fmaf(wp[k], ap[k], s);
-  for (int d = 32; d > 0; d >>= 1) s += __shfl_down(s, d, 64);
-  __shared__ float lds[FBLK / 64];
-  if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float t = b3[j];
-    for (int w = 0; w < FBLK / 64; ++w) t += lds[w];
-    int i = b * 128 + j;
-    z3[i] = t;
-    float r = t > 0.f ? t : 0.f;
-    unsigned char keep = 1;
-    if (p2 > 0.f) {
-      hiprandStatePhilox4_32_10_t st;
-      hiprand_init(seed ^ 0x9e3779b97f4a7c15ull, (unsigned long long)i,
-                   offset, &st);
-      keep = hiprand_uniform(&st) >= p2;
-    }
-    m3[i] = keep;
-    a3[i] = keep ? r / (1.f - p2) : 0.f;
-  }
-}
-
-// logits = W4 @ a3 + b4 ; softmax ; loss += -log p[target]/B ;
-// dlogit = (p - onehot)/B.  One block per sample row.
-__global__ void k_fc2_loss_fwd(const float* __restrict__ a3,
-                               const float* __restrict__ w4,
-                               const float* __restrict__ b4,
-                               const int* __restrict__ yb, int B, int C,
-                               float* __restrict__ dlogits,
-                               float* __restrict__ loss_acc) {
-  extern __shared__ float sm[];  // C floats
-  int b = blockIdx.x;
-  const float* ap = a3 + (long long)b * 128;
-  for (int j = threadIdx.x; j < C; j += blockDim.x) {
-    const float* wp = w4 + (long long)j * 128;
-    float s = b4[j];
-    #pragma unroll 4
-    for (int k = 0; k < 128; ++k) s = fmaf(wp[k], ap[k], s);
-    sm[j] = s;
-  }
-  __syncthreads();
-  // softmax over C (single wave handles it: C <= 1024 assumed small)
-  if (threadIdx.x == 0) {
-    float mx = sm[0];
-    for (int j = 1; j < C; ++j) mx = fmaxf(mx, sm[j]);
-    float z = 0.f;
-    for (int j = 0; j < C; ++j) { sm[j] = __expf(sm[j] - mx); z += sm[j]; }
-    float inv = 1.f / z;
-    int t = yb[b];
-    for (int j = 0; j < C; ++j) {
-      float p = sm[j] * inv;
-      dlogits[(long long)b * C + j] = (p - (j == t ? 1.f : 0.f)) / (float)B;
-    }
-    atomicAdd(loss_acc, -__logf(fmaxf(sm[t] * inv, 1e-30f)) / (float)B);
-  }
-}
-
-// ---------------------------------------------------------------------------
-// backward
-// ---------------------------------------------------------------------------
-// dW4[j,k] = sum_b dlogits[b,j]*a3[b,k]; db4[j] = sum_b dlogits[b,j]
-__global__ void k_fc2_bwd_w(const float* __restrict__ dlogits,
-                            const float* __restrict__ a3, int B, int C,
-                            float* __restrict__ dw4, float* __restrict__ db4) {
-  int total = C * 128;
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total;
-       i += gridDim.x * blockDim.x) {
-    int k = i % 128, j = i / 128;
-    float s = 0.f, sb = 0.f;
-    for (int b = 0; b < B; ++b) {
-      float d = dlogits[(long long)b * C + j];
-      s = fmaf(d, a3[(long long)b * 128 + k], s);
-      if (k == 0) sb += d;
-    }
-    dw4[i] = s;
-    if (k == 0) db4[j] = sb;
-  }
-}
-
-// dz3[b,k] = (sum_j dlogits[b,j]*W4[j,k]) * m3/(1-p2) * (z3>0)
-__global__ void k_fc2_bwd_x(const float* __restrict__ dlogits,
-                            const float* __restrict__ w4,
-                            const float* __restrict__ z3,
-                            const unsigned char* __restrict__ m3, int B,
-                            int C, float p2, float* __restrict__ dz3) {
-  int total = B * 128;
-  float inv_keep = 1.f / (1.f - p2);
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total;
-       i += gridDim.x * blockDim.x) {
-    int k = i % 128, b = i / 128;
-    float s = 0.f;
-    for (int j = 0; j < C; ++j)
-      s = fmaf(dlogits[(long long)b * C + j], w4[(long long)j * 128 + k], s);
-    float g = (p2 > 0.f) ? (m3[i] ? s * inv_keep : 0.f) : s;
-    dz3[i] = z3[i] > 0.f ? g : 0.f;
-  }
-}
-
-// dW3[j,k] = sum_b dz3[b,j]*a2[b,k]; db3[j] = sum_b dz3[b,j]
-__global__ void k_fc1_bwd_w(const float* __restrict__ dz3,
-                            const float* __restrict__ a2, int B,
-                            float* __restrict__ dw3, float* __restrict__ db3) {
-  long long total = 128LL * 9216;
+__global__ void k_w2_layouts_mb(const float* __restrict__ params,
+                                long long P, long long ow2, int K,
+                                float* __restrict__ w2t_stack,
+                                float* __restrict__ w2rot_stack) {
+  long long total = (long long)K * 18432;
   for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
        i < total; i += (long long)gridDim.x * blockDim.x) {
-    int k = (int)(i % 9216), j = (int)(i / 9216);
-    float s = 0.f, sb = 0.f;
-    for (int b = 0; b < B; ++b) {
-      float d = dz3[b * 128 + j];
-      s = fmaf(d, a2[(long long)b * 9216 + k], s);
-      if (k == 0) sb += d;
-    }
-    dw3[i] = s;
-    if (k == 0) db3[j] = sb;
+    int k = (int)(i / 18432), r = (int)(i % 18432);
+    int co = r / 288, kk = r % 288;
+    float v = params[(long long)k * P + ow2 + r];
+    w2t_stack[(long long)k * 18432 + kk * 64 + co] = v;
+    int rem = kk % 9;
+    w2rot_stack[(long long)k * 18432 + ((long long)co * 9 + rem) * 32
+                + kk / 9] = v;
   }
 }
 
-// d_a2[b,k] = sum_j dz3[b,j] * W3[j,k]  (then dropout1 bwd is fused in
-// the pool scatter)
-__global__ void k_fc1_bwd_x(const float* __restrict__ dz3,
-                            const float* __restrict__ w3, int B,
-                            float* __restrict__ da2) {
-  long long total = (long long)B * 9216;
-  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
-       i < total; i += (long long)gridDim.x * blockDim.x) {
-    int k = (int)(i % 9216), b = (int)(i / 9216);
-    const float* dp = dz3 + b * 128;
-    float s = 0.f;
-    #pragma unroll 4
-    for (int j = 0; j < 128; ++j)
-      s = fmaf(dp[j], w3[(long long)j * 9216 + k], s);
-    da2[i] = s;
-  }
-}
-
-// dropout1 bwd + maxpool scatter + relu bwd: one thread per pool cell
-// writes its 2x2 input cells (exactly one gets the grad)
-__global__ void k_pool_drop_bwd(const float* __restrict__ da2,
-                                const unsigned char* __restrict__ pidx,
-                                const unsigned char* __restrict__ m2,
-                                const float* __restrict__ r2, int B, float p1,
-                                float* __restrict__ dz2) {
-  int total = B * 64 * 144;
-  float inv_keep = (p1 < 1.f) ? 1.f / (1.f - p1) : 0.f;
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total;
-       i += gridDim.x * blockDim.x) {
-    int px = i % 12, py = (i / 12) % 12, c = (i / 144) % 64, b = i / 9216;
-    float g = (p1 > 0.f) ? (m2[i] ? da2[i] * inv_keep : 0.f) : da2[i];
-    int idx = pidx[i];
-    long long base = (((long long)b * 64 + c) * 24 + 2 * py) * 24 + 2 * px;
-    #pragma unroll
-    for (int d = 0; d < 4; ++d) {
-      long long o = base + (d >> 1) * 24 + (d & 1);
-      float v = (d == idx && r2[o] > 0.f) ? g : 0.f;
-      dz2[o] = v;
-    }
-  }
-}
-
-// dW2[co,ci,kh,kw] = sum_{b,y,x} a1[b,ci,y+kh,x+kw] * dz2[b,co,y,x]
-// one block per (co,ci) pair: 9 kernel taps reduced across 256 threads
-__global__ void k_conv2_bwd_w(const float* __restrict__ a1,
-                              const float* __restrict__ dz2, int B,
-                              float* __restrict__ dw2,
-                              float* __restrict__ db2) {
-  int co = blockIdx.x / 32, ci = blockIdx.x % 32;
-  float acc[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-  float accb = 0.f;
-  for (int t = threadIdx.x; t < B * 576; t += blockDim.x) {
-    int o = t % 576, b = t / 576;
-    int xx = o % 24, yy = o / 24;
-    float d = dz2[((long long)b * 64 + co) * 576 + o];
-    const float* ap = a1 + ((long long)b * 32 + ci) * 676 + yy * 26 + xx;
-    #pragma unroll
-    for (int kh = 0; kh < 3; ++kh)
-      #pragma unroll
-      for (int kw = 0; kw < 3; ++kw)
-        acc[kh * 3 + kw] = fmaf(ap[kh * 26 + kw], d, acc[kh * 3 + kw]);
-    if (ci == 0) accb += d;
-  }
-  __shared__ float lds[FBLK / 64 * 10];
-  int wave = threadIdx.x / 64, lane = threadIdx.x % 64;
-  #pragma unroll
-  for (int k = 0; k < 9; ++k) {
-    float s = acc[k];
-    for (int d = 32; d > 0; d >>= 1) s += __shfl_down(s, d, 64);
-    if (lane == 0) lds[wave * 10 + k] = s;
-  }
-  float sb = accb;
-  for (int d = 32; d > 0; d >>= 1) sb += __shfl_down(sb, d, 64);
-  if (lane == 0) lds[wave * 10 + 9] = sb;
-  __syncthreads();
-  if (threadIdx.x < 9) {
-    float s = 0.f;
-    for (int w = 0; w < FBLK / 64; ++w) s += lds[w * 10 + threadIdx.x];
-    dw2[(long long)(co * 32 + ci) * 9 + threadIdx.x] = s;
-  }
-  if (threadIdx.x == 9 && ci == 0) {
-    float s = 0.f;
-    for (int w = 0; w < FBLK / 64; ++w) s += lds[w * 10 + 9];
-    db2[co] = s;
-  }
-}
-
-// dz1[b,ci,p,q] = relu'(a1) * sum_{co,kh,kw valid} W2[co,ci,kh,kw] *
-//                 dz2[b,co,p-kh,q-kw]
-// Flat one-thread-per-output form: the LDS-tiled variant measured SLOWER
-// (160 blocks underfill the 256-CU chip and serialize on barriers); here
-// W2 (72 KB) and the dz2 rows stream through L2 instead.
-__global__ void k_conv2_bwd_x(const float* __restrict__ dz2,
-                              const float* __restrict__ w2,
-                              const float* __restrict__ a1, int B,
-                              float* __restrict__ dz1) {
-  int total = B * 32 * 676;
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total;
-       i += gridDim.x * blockDim.x) {
-    int q = i % 26, p = (i / 26) % 26, ci = (i / 676) % 32, b = i / 21632;
-    if (a1[i] <= 0.f) { dz1[i] = 0.f; continue; }
-    float s = 0.f;
-    #pragma unroll
-    for (int kh = 0; kh < 3; ++kh) {
-      int y = p - kh;
-      if (y < 0 || y >= 24) continue;
-      #pragma unroll
-      for (int kw = 0; kw < 3; ++kw) {
-        int x = q - kw;
-        if (x < 0 || x >= 24) continue;
-        for (int co = 0; co < 64; ++co)
-          s = fmaf(w2[((long long)co * 32 + ci) * 9 + kh * 3 + kw],
-                   dz2[((long long)b * 64 + co) * 576 + y * 24 + x], s);
-      }
-    }
-    dz1[i] = s;
-  }
-}
-
-// dW1[co,kh,kw] = sum_{b,y,x} x[b,y+kh,x+kw] * dz1[b,co,y,x]; db1 likewise
-__global__ void k_conv1_bwd_w(const float* __restrict__ x,
-                              const float* __restrict__ dz1, int B,
-                              float* __restrict__ dw1,
-                              float* __restrict__ db1) {
-  int co = blockIdx.x;  // 32 blocks
-  float acc[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-  float accb = 0.f;
-  for (int t = threadIdx.x; t < B * 676; t += blockDim.x) {
-    int o = t % 676, b = t / 676;
-    int xx = o % 26, yy = o / 26;
-    float d = dz1[((long long)b * 32 + co) * 676 + o];
-    const float* xp = x + b * 784 + yy * 28 + xx;
-    #pragma unroll
-    for (int kh = 0; kh < 3; ++kh)
-      #pragma unroll
-      for (int kw = 0; kw < 3; ++kw)
-        acc[kh * 3 + kw] = fmaf(xp[kh * 28 + kw], d, acc[kh * 3 + kw]);
-    accb += d;
-  }
-  __shared__ float lds[16 * 10];  // up to 16 waves (1024-thread blocks)
-  int n_waves = blockDim.x / 64;
-  int wave = threadIdx.x / 64, lane = threadIdx.x % 64;
-  #pragma unroll
-  for (int k = 0; k < 9; ++k) {
-    float s = acc[k];
-    for (int d = 32; d > 0; d >>= 1) s += __shfl_down(s, d, 64);
-    if (lane == 0) lds[wave * 10 + k] = s;
-  }
-  float sb = accb;
-  for (int d = 32; d > 0; d >>= 1) sb += __shfl_down(sb, d, 64);
-  if (lane == 0) lds[wave * 10 + 9] = sb;
-  __syncthreads();
-  if (threadIdx.x < 9) {
-    float s = 0.f;
-    for (int w = 0; w < n_waves; ++w) s += lds[w * 10 + threadIdx.x];
-    dw1[co * 9 + threadIdx.x] = s;
-  }
-  if (threadIdx.x == 9) {
-    float s = 0.f;
-    for (int w = 0; w < n_waves; ++w) s += lds[w * 10 + 9];
-    db1[co] = s;
-  }
-}
-
-// ---------------------------------------------------------------------------
-// MFMA implicit-GEMM forms of the profile-dominant kernels (round-1
-// profile: k_fc1_fwd 18.3%, k_conv2_bwd_x 18.3%, k_conv2_fwd 16.6%,
-// k_conv2_bwd_w 12.5% — profiles/r01_bench_kernel_stats_final.md).
-// gfx950's f32-input MFMA (v_mfma_f32_16x16x4_f32) is EXACT f32 — a
-// k-ordered fmaf chain at the full f32 rate — so these keep fp32
-// numerics while moving the matrix work onto the matrix pipe and leaving
-// the VALU free for address math and epilogues.
-//
-// Fragment maps (guide §3): A[i=l&15][k=l>>4], B[k=l>>4][j=l&15] one f32
-// VGPR each; D[row=(l>>4)*4+r][col=l&15], 4 f32 per lane.
-// ---------------------------------------------------------------------------
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-
-// W2 fragment layouts, rebuilt once per batch (the SGD step changes W2):
-// w2t[k=(ci,kh,kw)][co]   — conv2-fwd B operand, lane-contiguous in co
-// w2rot[k=(co,kh,kw)][ci] — conv2-bwd-data B operand, lane-contiguous in ci
-__global__ void k_w2_layouts(const float* __restrict__ w2,
-                             float* __restrict__ w2t,
-                             float* __restrict__ w2rot) {
-  int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= 18432) return;
-  int co = i / 288, k = i % 288;
-  float v = w2[i];
-  w2t[k * 64 + co] = v;
-  int ci = k / 9, rem = k % 9;
-  w2rot[(co * 9 + rem) * 32 + ci] = v;
-}
-
-// dz2 transposed to [b][o][co] (written into ws.r2, which is free after
-// pool_drop_bwd) — conv2-bwd-weight A operand, lane-contiguous in co
-__global__ void k_dz2_transpose(const float* __restrict__ dz2, int B,
-                                float* __restrict__ dz2t) {
-  int total = B * 36864;
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total;
-       i += gridDim.x * blockDim.x) {
-    int b = i / 36864, r = i % 36864, o = r / 64, co = r % 64;
-    dz2t[i] = dz2[((long long)b * 64 + co) * 576 + o];
-  }
-}
-
-// conv2 forward as implicit GEMM: out[(b,o),co] = sum_k a1im2col[(b,o),k]
-// * W2^T[k,co], M=576/batch-row (exact 36 16-tiles), N=64, K=288.
-// One block per (b, 64-row M-tile); a1[b] (86.5 KB) staged once in LDS.
+// conv2 forward (f32 MFMA): grid = G * 9 blocks; per-block client k
 __global__ __launch_bounds__(256)
-void k_conv2_fwd_mfma(const float* __restrict__ a1,
-                      const float* __restrict__ w2t,
-                      const float* __restrict__ b2, int B,
-                      float* __restrict__ r2) {
+void k_conv2_fwd_mfma_mb(const float* __restrict__ a1,
+                         const float* __restrict__ w2t_stack,
+                         const float* __restrict__ params, long long P,
+                         long long ob2, int bs, int K,
+                         float* __restrict__ r2) {
   __shared__ float lds[32 * 676];
-  int b = blockIdx.x / 9, mt = blockIdx.x % 9;
-  const float* src = a1 + (long long)b * 21632;
+  long long g = blockIdx.x / 9;
+  int mt = blockIdx.x % 9;
+  int k = (int)(g / bs);
+  const float* src = a1 + g * 21632;
   for (int i = threadIdx.x; i < 21632; i += 256) lds[i] = src[i];
   __syncthreads();
+  const float* w2t = w2t_stack + (long long)k * 18432;
+  const float* b2 = params + (long long)k * P + ob2;
   int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  int m = mt * 64 + w * 16 + (lane & 15);  // output cell o in [0,576)
+  int m = mt * 64 + w * 16 + (lane & 15);
   int yy = m / 24, xx = m % 24;
   int kc = lane >> 4;
   f32x4 acc[4] = {f32x4{0,0,0,0}, f32x4{0,0,0,0},
                   f32x4{0,0,0,0}, f32x4{0,0,0,0}};
+  #pragma unroll 4
   for (int k0 = 0; k0 < 288; k0 += 4) {
-    int k = k0 + kc;
-    int ci = k / 9, rem = k % 9, kh = rem / 3, kw = rem % 3;
+    int kk = k0 + kc;
+    int ci = kk / 9, rem = kk % 9, kh = rem / 3, kw = rem % 3;
     float a = lds[ci * 676 + (yy + kh) * 26 + xx + kw];
-    const float* wrow = w2t + (long long)k * 64 + (lane & 15);
+    const float* wrow = w2t + (long long)kk * 64 + (lane & 15);
     #pragma unroll
     for (int nt = 0; nt < 4; ++nt) {
-      float bv = wrow[nt * 16];  // lane-contiguous 64B group reads
+      float bv = wrow[nt * 16];
       acc[nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, bv, acc[nt], 0, 0, 0);
     }
   }
@@ -580,151 +230,109 @@ void k_conv2_fwd_mfma(const float* __restrict__ a1,
     for (int nt = 0; nt < 4; ++nt) {
       int co = nt * 16 + cl;
       float v = acc[nt][r] + b2[co];
-      r2[((long long)b * 64 + co) * 576 + om + r] = v > 0.f ? v : 0.f;
+      r2[(g * 64 + co) * 576 + om + r] = v > 0.f ? v : 0.f;
     }
 }
 
-// conv2 backward-data as implicit GEMM: dz1[(b,p,q),ci] = relu'(a1) *
-// sum_k dz2pad[(b,p,q),k] * W2rot[k,ci], M=676/batch-row (11 64-tiles,
-// masked tail), N=32, K=576 (co,kh,kw).  dz2[b] (147 KB) staged in LDS.
-__global__ __launch_bounds__(256)
-void k_conv2_bwd_x_mfma(const float* __restrict__ dz2,
-                        const float* __restrict__ w2rot,
-                        const float* __restrict__ a1, int B,
-                        float* __restrict__ dz1) {
-  __shared__ float lds[64 * 576];
-  int b = blockIdx.x / 11, mt = blockIdx.x % 11;
-  const float* src = dz2 + (long long)b * 36864;
-  for (int i = threadIdx.x; i < 36864; i += 256) lds[i] = src[i];
-  __syncthreads();
-  int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  int m = mt * 64 + w * 16 + (lane & 15);  // cell (p,q) in [0,676)
-  int p = m / 26, q = m % 26;
-  bool mrow = m < 676;
-  int kc = lane >> 4;
-  f32x4 acc[2] = {f32x4{0,0,0,0}, f32x4{0,0,0,0}};
-  for (int k0 = 0; k0 < 576; k0 += 4) {
-    int k = k0 + kc;
-    int co = k / 9, rem = k % 9, kh = rem / 3, kw = rem % 3;
-    int y = p - kh, x = q - kw;
-    float a = (mrow && y >= 0 && y < 24 && x >= 0 && x < 24)
-                  ? lds[co * 576 + y * 24 + x] : 0.f;
-    const float* wrow = w2rot + (long long)k * 32 + (lane & 15);
-    #pragma unroll
-    for (int nt = 0; nt < 2; ++nt) {
-      float bv = wrow[nt * 16];  // lane-contiguous 64B group reads
-      acc[nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, bv, acc[nt], 0, 0, 0);
-    }
+// maxpool 2x2 + dropout(p1) of pool cell i, whose 2x2 window starts at
+// `base`: a2 = keep ? max/(1-p1) : 0; save argmax + mask.  The Philox
+// key is (seed, li >> 2, batch offset) with li the CLIENT-LOCAL cell
+// index, so a client's masks do not depend on which driver or which
+// stack slot trains it.  Index is the wrapper's own index width (int
+// per client, long long for the stack).
+template <typename Index>
+__device__ __forceinline__ void pool_drop_cell(
+    const float* __restrict__ base, Index i, Index li, float p1,
+    float inv_keep, unsigned long long seed, unsigned long long offset,
+    float* __restrict__ a2, unsigned char* __restrict__ pidx,
+    unsigned char* __restrict__ m2) {
+  float v0 = base[0], v1 = base[1], v2 = base[24], v3 = base[25];
+  float m = v0; int idx = 0;
+  if (v1 > m) { m = v1; idx = 1; }
+  if (v2 > m) { m = v2; idx = 2; }
+  if (v3 > m) { m = v3; idx = 3; }
+  unsigned char keep = 1;
+  if (p1 > 0.f) {
+    // one Philox draw covers 4 cells (init is ~10 rounds — the cost)
+    hiprandStatePhilox4_32_10_t st;
+    hiprand_init(seed, (unsigned long long)(li >> 2), offset, &st);
+    float4 u = hiprand_uniform4(&st);
+    float uu = (li & 3) == 0 ? u.x : (li & 3) == 1 ? u.y
+               : (li & 3) == 2 ? u.z : u.w;
+    keep = uu >= p1;
   }
-  int om = mt * 64 + w * 16 + (lane >> 4) * 4;
-  int cl = lane & 15;
-  #pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    if (om + r >= 676) continue;
-    #pragma unroll
-    for (int nt = 0; nt < 2; ++nt) {
-      int ci = nt * 16 + cl;
-      long long o = ((long long)b * 32 + ci) * 676 + om + r;
-      dz1[o] = a1[o] > 0.f ? acc[nt][r] : 0.f;
-    }
+  pidx[i] = (unsigned char)idx;
+  m2[i] = keep;
+  a2[i] = keep ? m * inv_keep : 0.f;
+}
+
+__global__ void k_pool_drop_fwd(const float* __restrict__ r2, int B,
+                                float p1, unsigned long long seed,
+                                unsigned long long offset,
+                                float* __restrict__ a2,
+                                unsigned char* __restrict__ pidx,
+                                unsigned char* __restrict__ m2) {
+  int total = B * 64 * 144;
+  float inv_keep = (p1 < 1.f) ? 1.f / (1.f - p1) : 0.f;
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total;
+       i += gridDim.x * blockDim.x) {
+    int px = i % 12, py = (i / 12) % 12, c = (i / 144) % 64, b = i / 9216;
+    const float* base =
+        r2 + (((long long)b * 64 + c) * 24 + 2 * py) * 24 + 2 * px;
+    pool_drop_cell(base, i, i, p1, inv_keep, seed, offset, a2, pidx, m2);
   }
 }
 
-// conv2 weight gradient as GEMM: dW2[co,(ci,kh,kw)] = sum_{b,o}
-// dz2[(b,o),co] * a1im2col[(b,o),(ci,kh,kw)], M=64, N=288, K=B*576,
-// split over b: block (nb in 0..5, b) computes a 64x48 tile of the
-// per-b partial into ws.wsl[b]; k_conv2_bwd_w_fold sums the B slabs in
-// fixed order (deterministic — no atomics).  a1[b] staged in LDS.
-__global__ __launch_bounds__(256)
-void k_conv2_bwd_w_mfma(const float* __restrict__ dz2t,
-                        const float* __restrict__ a1, int B,
-                        float* __restrict__ slab) {
-  __shared__ float lds[32 * 676];
-  int nb = blockIdx.x % 6, b = blockIdx.x / 6;
-  const float* src = a1 + (long long)b * 21632;
-  for (int i = threadIdx.x; i < 21632; i += 256) lds[i] = src[i];
-  __syncthreads();
-  int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  int co = w * 16 + (lane & 15);
-  int kc = lane >> 4;
-  const float* dzb = dz2t + (long long)b * 36864;  // [o][co] layout
-  f32x4 acc[3] = {f32x4{0,0,0,0}, f32x4{0,0,0,0}, f32x4{0,0,0,0}};
-  for (int k0 = 0; k0 < 576; k0 += 4) {
-    int o = k0 + kc;
-    int yy = o / 24, xx = o % 24;
-    float a = dzb[o * 64 + co];  // lane-contiguous 64B group reads
-    #pragma unroll
-    for (int nt = 0; nt < 3; ++nt) {
-      int n = nb * 48 + nt * 16 + (lane & 15);
-      int ci = n / 9, rem = n % 9, kh = rem / 3, kw = rem % 3;
-      float bv = lds[ci * 676 + (yy + kh) * 26 + xx + kw];
-      acc[nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, bv, acc[nt], 0, 0, 0);
-    }
-  }
-  float* out = slab + (long long)b * 18432;
-  int orow = w * 16 + (lane >> 4) * 4;
-  int cl = lane & 15;
-  #pragma unroll
-  for (int r = 0; r < 4; ++r)
-    #pragma unroll
-    for (int nt = 0; nt < 3; ++nt)
-      out[(orow + r) * 288 + nb * 48 + nt * 16 + cl] = acc[nt][r];
-}
-
-// fold the B per-batch-row dW2 slabs (fixed order) + db2 column sums
-__global__ void k_conv2_bwd_w_fold(const float* __restrict__ slab, int B,
-                                   float* __restrict__ dw2) {
-  int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= 18432) return;
-  float s = 0.f;
-  for (int b = 0; b < B; ++b) s += slab[(long long)b * 18432 + i];
-  dw2[i] = s;
-}
-
-__global__ void k_conv2_bwd_b(const float* __restrict__ dz2, int B,
-                              float* __restrict__ db2) {
-  int co = blockIdx.x;
-  float s = 0.f;
-  for (int t = threadIdx.x; t < B * 576; t += blockDim.x) {
-    int o = t % 576, b = t / 576;
-    s += dz2[((long long)b * 64 + co) * 576 + o];
-  }
-  for (int d = 32; d > 0; d >>= 1) s += __shfl_down(s, d, 64);
-  __shared__ float lds[4];
-  if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float t = 0.f;
-    for (int k = 0; k < (int)blockDim.x / 64; ++k) t += lds[k];
-    db2[co] = t;
+__global__ void k_pool_drop_fwd_mb(const float* __restrict__ r2, int bs,
+                                   int K, float p1,
+                                   const long long* __restrict__ seeds,
+                                   unsigned long long offset,
+                                   float* __restrict__ a2,
+                                   unsigned char* __restrict__ pidx,
+                                   unsigned char* __restrict__ m2) {
+  long long total = (long long)K * bs * 9216;
+  float inv_keep = (p1 < 1.f) ? 1.f / (1.f - p1) : 0.f;
+  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+       i < total; i += (long long)gridDim.x * blockDim.x) {
+    int px = (int)(i % 12), py = (int)((i / 12) % 12);
+    int c = (int)((i / 144) % 64);
+    long long g = i / 9216;
+    int k = (int)(g / bs), b = (int)(g % bs);
+    const float* base = r2 + ((g * 64 + c) * 24 + 2 * py) * 24 + 2 * px;
+    long long li = (long long)b * 9216 + (i % 9216);
+    pool_drop_cell(base, i, li, p1, inv_keep, (unsigned long long)seeds[k],
+                   offset, a2, pidx, m2);
   }
 }
 
 // fc1 forward as split-K MFMA GEMM: z3^T[j,b] = sum_k W3[j,k]*a2[b,k],
-// M=128 (j), N=32 (b, masked to B), K=9216 split into FC1_SPLIT chunks;
-// per-chunk partials land in ws.wsl and k_fc1_fwd_reduce folds them in
-// fixed order + bias + relu + dropout (same Philox stream as the scalar
-// k_fc1_fwd, so masks are bit-identical to round 1's kernel).
+// M=128 (j), N=32 (b, masked to bs), K=9216 split into FC1_SPLIT chunks;
+// per-chunk partials land in the slab and k_fc1_fwd_reduce* folds them.
+// grid = K * FC1_SPLIT blocks.
 #define FC1_SPLIT 64
 #define FC1_CH (9216 / FC1_SPLIT)  /* 144 k per chunk */
 #define FC1_LD (FC1_CH + 1)        /* LDS row stride 145: odd multiplier of
                                       16 mod 32 -> conflict-free group reads */
 __global__ __launch_bounds__(256)
-void k_fc1_fwd_mfma(const float* __restrict__ a2,
-                    const float* __restrict__ w3, int B,
-                    float* __restrict__ slab) {
-  __shared__ float lw[128 * FC1_LD];  // W3 chunk [128][144] (72.5 KB)
-  __shared__ float la[32 * FC1_LD];   // a2 chunk [32][144]  (18.1 KB)
-  int s = blockIdx.x;                 // k-chunk
+void k_fc1_fwd_mfma_mb(const float* __restrict__ a2,
+                       const float* __restrict__ params, long long P,
+                       long long ow3, int bs, int K,
+                       float* __restrict__ slab) {
+  __shared__ float lw[128 * FC1_LD];
+  __shared__ float la[32 * FC1_LD];
+  int k = blockIdx.x / FC1_SPLIT;
+  int s = blockIdx.x % FC1_SPLIT;
   int k_base = s * FC1_CH;
+  const float* w3 = params + (long long)k * P + ow3;
+  const float* a2k = a2 + (long long)k * bs * 9216;
   for (int i = threadIdx.x; i < 128 * FC1_CH; i += 256) {
-    int row = i / FC1_CH, kk = i % FC1_CH;  // 576 B coalesced runs per row
+    int row = i / FC1_CH, kk = i % FC1_CH;
     lw[row * FC1_LD + kk] = w3[(long long)row * 9216 + k_base + kk];
   }
   for (int i = threadIdx.x; i < 32 * FC1_CH; i += 256) {
     int bu = i / FC1_CH, kk = i % FC1_CH;
-    la[bu * FC1_LD + kk] = bu < B ? a2[(long long)bu * 9216 + k_base + kk]
-                                  : 0.f;
+    la[bu * FC1_LD + kk] = bu < bs
+        ? a2k[(long long)bu * 9216 + k_base + kk] : 0.f;
   }
   __syncthreads();
   int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -732,27 +340,88 @@ void k_fc1_fwd_mfma(const float* __restrict__ a2,
   f32x4 acc[2][2] = {{f32x4{0,0,0,0}, f32x4{0,0,0,0}},
                      {f32x4{0,0,0,0}, f32x4{0,0,0,0}}};
   for (int k0 = 0; k0 < FC1_CH; k0 += 4) {
-    int k = k0 + kc;
-    float a0 = lw[(w * 32 + il) * FC1_LD + k];
-    float a1v = lw[(w * 32 + 16 + il) * FC1_LD + k];
+    int kk = k0 + kc;
+    float a0 = lw[(w * 32 + il) * FC1_LD + kk];
+    float a1v = lw[(w * 32 + 16 + il) * FC1_LD + kk];
     #pragma unroll
     for (int u = 0; u < 2; ++u) {
-      float bv = la[(u * 16 + il) * FC1_LD + k];
+      float bv = la[(u * 16 + il) * FC1_LD + kk];
       acc[0][u] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, bv, acc[0][u], 0, 0, 0);
       acc[1][u] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1v, bv, acc[1][u], 0, 0, 0);
     }
   }
+  float* slk = slab + (long long)k * FC1_SPLIT * bs * 128;
   #pragma unroll
-  for (int t = 0; t < 2; ++t)
+  for (int tt = 0; tt < 2; ++tt)
     #pragma unroll
     for (int u = 0; u < 2; ++u) {
       int bu = u * 16 + il;
-      if (bu >= B) continue;
-      int j = w * 32 + t * 16 + (lane >> 4) * 4;
+      if (bu >= bs) continue;
+      int j = w * 32 + tt * 16 + (lane >> 4) * 4;
       #pragma unroll
       for (int r = 0; r < 4; ++r)
-        slab[((long long)s * B + bu) * 128 + j + r] = acc[t][u][r];
+        slk[((long long)s * bs + bu) * 128 + j + r] = acc[tt][u][r];
     }
+}
+
+// fold one client's SPLIT split-K partials for (row b, unit j) in fixed
+// order (deterministic — no atomics) + bias + relu + dropout(p2) into
+// element i of z3/a3/m3.  Philox key: (seed ^ golden ratio, li, batch
+// offset) with li = b*128 + j the CLIENT-LOCAL element index.
+template <int SPLIT>
+__device__ __forceinline__ void fc1_reduce_elem(
+    const float* __restrict__ slk, float bias, int bs, int b, int j,
+    long long i, long long li, float p2, unsigned long long seed,
+    unsigned long long offset, float* __restrict__ z3,
+    float* __restrict__ a3, unsigned char* __restrict__ m3) {
+  float t = bias;
+  for (int s = 0; s < SPLIT; ++s)
+    t += slk[((long long)s * bs + b) * 128 + j];
+  z3[i] = t;
+  float r = t > 0.f ? t : 0.f;
+  unsigned char keep = 1;
+  if (p2 > 0.f) {
+    hiprandStatePhilox4_32_10_t st;
+    hiprand_init(seed ^ 0x9e3779b97f4a7c15ull, (unsigned long long)li,
+                 offset, &st);
+    keep = hiprand_uniform(&st) >= p2;
+  }
+  m3[i] = keep;
+  a3[i] = keep ? r / (1.f - p2) : 0.f;
+}
+
+template <int SPLIT>
+__device__ __forceinline__ void fc1_reduce_client(
+    const float* __restrict__ slab, const float* __restrict__ b3, int B,
+    float p2, unsigned long long seed, unsigned long long offset,
+    float* __restrict__ z3, float* __restrict__ a3,
+    unsigned char* __restrict__ m3) {
+  int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= B * 128) return;
+  int b = i / 128, j = i % 128;
+  fc1_reduce_elem<SPLIT>(slab, b3[j], B, b, j, i, i, p2, seed, offset,
+                         z3, a3, m3);
+}
+
+template <int SPLIT>
+__device__ __forceinline__ void fc1_reduce_stack(
+    const float* __restrict__ slab, const float* __restrict__ params,
+    long long P, long long ob3, int bs, int K, float p2,
+    const long long* __restrict__ seeds, unsigned long long offset,
+    float* __restrict__ z3, float* __restrict__ a3,
+    unsigned char* __restrict__ m3) {
+  long long total = (long long)K * bs * 128;
+  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+       i < total; i += (long long)gridDim.x * blockDim.x) {
+    long long g = i / 128;
+    int j = (int)(i % 128);
+    int k = (int)(g / bs), b = (int)(g % bs);
+    fc1_reduce_elem<SPLIT>(slab + (long long)k * SPLIT * bs * 128,
+                           params[(long long)k * P + ob3 + j], bs, b, j, i,
+                           (long long)b * 128 + j, p2,
+                           (unsigned long long)seeds[k], offset,
+                           z3, a3, m3);
+  }
 }
 
 __global__ void k_fc1_fwd_reduce(const float* __restrict__ slab,
@@ -762,78 +431,197 @@ __global__ void k_fc1_fwd_reduce(const float* __restrict__ slab,
                                  float* __restrict__ z3,
                                  float* __restrict__ a3,
                                  unsigned char* __restrict__ m3) {
-  int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= B * 128) return;
-  int b = i / 128, j = i % 128;
-  float t = b3[j];
-  for (int s = 0; s < FC1_SPLIT; ++s)
-    t += slab[((long long)s * B + b) * 128 + j];
-  z3[i] = t;
-  float r = t > 0.f ? t : 0.f;
-  unsigned char keep = 1;
-  if (p2 > 0.f) {
-    hiprandStatePhilox4_32_10_t st;
-    hiprand_init(seed ^ 0x9e3779b97f4a7c15ull, (unsigned long long)i,
-                 offset, &st);
-    keep = hiprand_uniform(&st) >= p2;
-  }
-  m3[i] = keep;
-  a3[i] = keep ? r / (1.f - p2) : 0.f;
+  fc1_reduce_client<FC1_SPLIT>(slab, b3, B, p2, seed, offset, z3, a3, m3);
 }
 
-// dW3[j,n] = sum_b dz3[b,j]*a2[b,n]: M=128, N=9216, K=B (<=32, masked).
-// Block = 128x64 tile (wave: 2 m-tiles x 4 n-tiles), grid = 144.
+__global__ void k_fc1_fwd_reduce_mb(const float* __restrict__ slab,
+                                    const float* __restrict__ params,
+                                    long long P, long long ob3, int bs,
+                                    int K, float p2,
+                                    const long long* __restrict__ seeds,
+                                    unsigned long long offset,
+                                    float* __restrict__ z3,
+                                    float* __restrict__ a3,
+                                    unsigned char* __restrict__ m3) {
+  fc1_reduce_stack<FC1_SPLIT>(slab, params, P, ob3, bs, K, p2, seeds, offset,
+                              z3, a3, m3);
+}
+
+// fc2 + softmax + CE for one sample row (one block): logits = W4 @ a3 +
+// b4 ; softmax ; *loss += -log p[target]/Bk ; dlogit = (p - onehot)/Bk,
+// Bk the row count of the client's batch.  sm holds C floats of LDS.
+__device__ __forceinline__ void fc2_loss_row(
+    const float* __restrict__ ap, const float* __restrict__ w4,
+    const float* __restrict__ b4, int target, int Bk, int C,
+    float* __restrict__ dl, float* __restrict__ loss, float* sm) {
+  for (int j = threadIdx.x; j < C; j += blockDim.x) {
+    const float* wp = w4 + (long long)j * 128;
+    float s = b4[j];
+    #pragma unroll 4
+    for (int kk = 0; kk < 128; ++kk) s = fmaf(wp[kk], ap[kk], s);
+    sm[j] = s;
+  }
+  __syncthreads();
+  // one thread does the softmax: C is small
+  if (threadIdx.x == 0) {
+    float mx = sm[0];
+    for (int j = 1; j < C; ++j) mx = fmaxf(mx, sm[j]);
+    float z = 0.f;
+    for (int j = 0; j < C; ++j) { sm[j] = __expf(sm[j] - mx); z += sm[j]; }
+    float inv = 1.f / z;
+    for (int j = 0; j < C; ++j) {
+      float p = sm[j] * inv;
+      dl[j] = (p - (j == target ? 1.f : 0.f)) / (float)Bk;
+    }
+    atomicAdd(loss, -__logf(fmaxf(sm[target] * inv, 1e-30f)) / (float)Bk);
+  }
+}
+
+__global__ void k_fc2_loss_fwd(const float* __restrict__ a3,
+                               const float* __restrict__ w4,
+                               const float* __restrict__ b4,
+                               const int* __restrict__ yb, int B, int C,
+                               float* __restrict__ dlogits,
+                               float* __restrict__ loss_acc) {
+  extern __shared__ float sm[];
+  int b = blockIdx.x;
+  fc2_loss_row(a3 + (long long)b * 128, w4, b4, yb[b], B, C,
+               dlogits + (long long)b * C, loss_acc, sm);
+}
+
+// one block per super-row g; yb<0 (inactive) rows zero their dlogits
+__global__ void k_fc2_loss_fwd_mb(const float* __restrict__ a3,
+                                  const float* __restrict__ params,
+                                  long long P, long long ow4, long long ob4,
+                                  const long long* __restrict__ counts,
+                                  int t, int bs, int K, int C,
+                                  const int* __restrict__ yb,
+                                  float* __restrict__ dlogits,
+                                  float* __restrict__ loss_out) {
+  extern __shared__ float sm[];
+  long long g = blockIdx.x;
+  int k = (int)(g / bs);
+  int target = yb[g];
+  if (target < 0) {
+    for (int j = threadIdx.x; j < C; j += blockDim.x)
+      dlogits[g * C + j] = 0.f;
+    return;
+  }
+  fc2_loss_row(a3 + g * 128, params + (long long)k * P + ow4,
+               params + (long long)k * P + ob4, target,
+               mega_Bk(counts, k, t, bs), C, dlogits + g * C, loss_out + k,
+               sm);
+}
+
+// fc2 backward (weights): grid = K * ceil(C*128/256)
+__global__ void k_fc2_bwd_w_mb(const float* __restrict__ dlogits,
+                               const float* __restrict__ a3,
+                               float* __restrict__ grads, long long P,
+                               long long ow4, long long ob4, int bs, int K,
+                               int C) {
+  int per_k = (C * 128 + FBLK - 1) / FBLK;
+  int k = blockIdx.x / per_k;
+  int i0 = (blockIdx.x % per_k) * FBLK + threadIdx.x;
+  if (i0 >= C * 128) return;
+  int kk = i0 % 128, j = i0 / 128;
+  const float* dlk = dlogits + (long long)k * bs * C;
+  const float* a3k = a3 + (long long)k * bs * 128;
+  float s = 0.f, sb = 0.f;
+  for (int b = 0; b < bs; ++b) {
+    float d = dlk[(long long)b * C + j];
+    s = fmaf(d, a3k[(long long)b * 128 + kk], s);
+    if (kk == 0) sb += d;
+  }
+  grads[(long long)k * P + ow4 + i0] = s;
+  if (kk == 0) grads[(long long)k * P + ob4 + j] = sb;
+}
+
+__global__ void k_fc2_bwd_x_mb(const float* __restrict__ dlogits,
+                               const float* __restrict__ params, long long P,
+                               long long ow4, const float* __restrict__ z3,
+                               const unsigned char* __restrict__ m3, int bs,
+                               int K, int C, float p2,
+                               float* __restrict__ dz3) {
+  long long total = (long long)K * bs * 128;
+  float inv_keep = 1.f / (1.f - p2);
+  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+       i < total; i += (long long)gridDim.x * blockDim.x) {
+    int kk = (int)(i % 128);
+    long long g = i / 128;
+    int k = (int)(g / bs);
+    const float* w4 = params + (long long)k * P + ow4;
+    const float* dl = dlogits + g * C;
+    float s = 0.f;
+    for (int j = 0; j < C; ++j)
+      s = fmaf(dl[j], w4[(long long)j * 128 + kk], s);
+    float gg = (p2 > 0.f) ? (m3[i] ? s * inv_keep : 0.f) : s;
+    dz3[i] = z3[i] > 0.f ? gg : 0.f;
+  }
+}
+
+// fc1 backward weights (f32 MFMA): grid = K * 144
 __global__ __launch_bounds__(256)
-void k_fc1_bwd_w_mfma(const float* __restrict__ dz3,
-                      const float* __restrict__ a2, int B,
-                      float* __restrict__ dw3) {
-  int nblk = blockIdx.x;                  // 64-col slab of N
+void k_fc1_bwd_w_mfma_mb(const float* __restrict__ dz3,
+                         const float* __restrict__ a2,
+                         float* __restrict__ grads, long long P,
+                         long long ow3, int bs, int K) {
+  int k = blockIdx.x / 144;
+  int nblk = blockIdx.x % 144;
+  const float* dz = dz3 + (long long)k * bs * 128;
+  const float* a2k = a2 + (long long)k * bs * 9216;
+  float* dw3 = grads + (long long)k * P + ow3;
   int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   int kc = lane >> 4, il = lane & 15;
   f32x4 acc[2][4] = {{f32x4{0,0,0,0}, f32x4{0,0,0,0}, f32x4{0,0,0,0}, f32x4{0,0,0,0}},
                      {f32x4{0,0,0,0}, f32x4{0,0,0,0}, f32x4{0,0,0,0}, f32x4{0,0,0,0}}};
-  for (int k0 = 0; k0 < ((B + 3) & ~3); k0 += 4) {
+  for (int k0 = 0; k0 < ((bs + 3) & ~3); k0 += 4) {
     int b = k0 + kc;
-    bool kv = b < B;
-    float a0 = kv ? dz3[(long long)b * 128 + w * 32 + il] : 0.f;
-    float a1v = kv ? dz3[(long long)b * 128 + w * 32 + 16 + il] : 0.f;
+    bool kv = b < bs;
+    float a0 = kv ? dz[(long long)b * 128 + w * 32 + il] : 0.f;
+    float a1v = kv ? dz[(long long)b * 128 + w * 32 + 16 + il] : 0.f;
     #pragma unroll
     for (int nt = 0; nt < 4; ++nt) {
       long long n = (long long)nblk * 64 + nt * 16 + il;
-      float bv = kv ? a2[(long long)b * 9216 + n] : 0.f;
+      float bv = kv ? a2k[(long long)b * 9216 + n] : 0.f;
       acc[0][nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, bv, acc[0][nt], 0, 0, 0);
       acc[1][nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1v, bv, acc[1][nt], 0, 0, 0);
     }
   }
   #pragma unroll
-  for (int t = 0; t < 2; ++t) {
-    int j = w * 32 + t * 16 + (lane >> 4) * 4;
+  for (int tt = 0; tt < 2; ++tt) {
+    int j = w * 32 + tt * 16 + (lane >> 4) * 4;
     #pragma unroll
     for (int r = 0; r < 4; ++r)
       #pragma unroll
       for (int nt = 0; nt < 4; ++nt)
         dw3[(long long)(j + r) * 9216 + nblk * 64 + nt * 16 + il] =
-            acc[t][nt][r];
+            acc[tt][nt][r];
   }
 }
 
-__global__ void k_fc1_bwd_b(const float* __restrict__ dz3, int B,
-                            float* __restrict__ db3) {
-  int j = blockIdx.x * blockDim.x + threadIdx.x;
+__global__ void k_fc1_bwd_b_mb(const float* __restrict__ dz3,
+                               float* __restrict__ grads, long long P,
+                               long long ob3, int bs, int K) {
+  int k = blockIdx.x;
+  int j = threadIdx.x;
   if (j >= 128) return;
+  const float* dz = dz3 + (long long)k * bs * 128;
   float s = 0.f;
-  for (int b = 0; b < B; ++b) s += dz3[(long long)b * 128 + j];
-  db3[j] = s;
+  for (int b = 0; b < bs; ++b) s += dz[(long long)b * 128 + j];
+  grads[(long long)k * P + ob3 + j] = s;
 }
 
-// da2[b,n] = sum_j dz3[b,j]*W3[j,n]: M=32 (b, masked to B), N=9216,
-// K=128.  Block = 32x64 tile (wave: 1 n-tile of 16 cols x 2 m-tiles),
-// grid = 144.
+// fc1 backward data (f32 MFMA): grid = K * 144
 __global__ __launch_bounds__(256)
-void k_fc1_bwd_x_mfma(const float* __restrict__ dz3,
-                      const float* __restrict__ w3, int B,
-                      float* __restrict__ da2) {
-  int nblk = blockIdx.x;
+void k_fc1_bwd_x_mfma_mb(const float* __restrict__ dz3,
+                         const float* __restrict__ params, long long P,
+                         long long ow3, int bs, int K,
+                         float* __restrict__ da2) {
+  int k = blockIdx.x / 144;
+  int nblk = blockIdx.x % 144;
+  const float* dz = dz3 + (long long)k * bs * 128;
+  const float* w3 = params + (long long)k * P + ow3;
+  float* da = da2 + (long long)k * bs * 9216;
   int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   int kc = lane >> 4, il = lane & 15;
   f32x4 acc[2] = {f32x4{0,0,0,0}, f32x4{0,0,0,0}};
@@ -842,46 +630,353 @@ void k_fc1_bwd_x_mfma(const float* __restrict__ dz3,
     long long n = (long long)nblk * 64 + w * 16 + il;
     float bv = w3[(long long)j * 9216 + n];
     #pragma unroll
-    for (int t = 0; t < 2; ++t) {
-      int bu = t * 16 + il;
-      float a = bu < B ? dz3[(long long)bu * 128 + j] : 0.f;
-      acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, bv, acc[t], 0, 0, 0);
+    for (int tt = 0; tt < 2; ++tt) {
+      int bu = tt * 16 + il;
+      float a = bu < bs ? dz[(long long)bu * 128 + j] : 0.f;
+      acc[tt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, bv, acc[tt], 0, 0, 0);
     }
   }
   #pragma unroll
-  for (int t = 0; t < 2; ++t) {
-    int bu = t * 16 + (lane >> 4) * 4;
+  for (int tt = 0; tt < 2; ++tt) {
+    int bu = tt * 16 + (lane >> 4) * 4;
     #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      if (bu + r >= B) continue;
-      da2[(long long)(bu + r) * 9216 + (long long)nblk * 64 + w * 16 + il] =
-          acc[t][r];
+      if (bu + r >= bs) continue;
+      da[(long long)(bu + r) * 9216 + (long long)nblk * 64 + w * 16 + il] =
+          acc[tt][r];
     }
   }
 }
 
-// ---------------------------------------------------------------------------
-// epoch driver: the ONLY host entry — loops every batch of one client's
-// local epoch, launching fwd/bwd + fused clip-stats + SGD per batch.
-// ---------------------------------------------------------------------------
-
-extern "C" {
-void launch_sum_sumsq2(const float*, long long, double*, double*, hipStream_t);
-void launch_clip_apply_stats(float*, long long, const double*, float, float,
-                             float*, hipStream_t);
-void launch_sgd_step(float*, const float*, float*, float, const float*, float,
-                     float, float, int, int, long long, hipStream_t);
+__global__ void k_pool_drop_bwd_mb(const float* __restrict__ da2,
+                                   const unsigned char* __restrict__ pidx,
+                                   const unsigned char* __restrict__ m2,
+                                   const float* __restrict__ r2, int bs,
+                                   int K, float p1,
+                                   float* __restrict__ dz2) {
+  long long total = (long long)K * bs * 9216;
+  float inv_keep = (p1 < 1.f) ? 1.f / (1.f - p1) : 0.f;
+  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+       i < total; i += (long long)gridDim.x * blockDim.x) {
+    int px = (int)(i % 12), py = (int)((i / 12) % 12);
+    int c = (int)((i / 144) % 64);
+    long long g = i / 9216;
+    float gg = (p1 > 0.f) ? (m2[i] ? da2[i] * inv_keep : 0.f) : da2[i];
+    int idx = pidx[i];
+    long long base = ((g * 64 + c) * 24 + 2 * py) * 24 + 2 * px;
+    #pragma unroll
+    for (int d = 0; d < 4; ++d) {
+      long long o = base + (d >> 1) * 24 + (d & 1);
+      dz2[o] = (d == idx && r2[o] > 0.f) ? gg : 0.f;
+    }
+  }
 }
 
-struct CnnWorkspace {
-  // laid out inside one float buffer by the binding (sizes for B rows)
-  float *xb, *a1, *r2, *a2, *z3, *a3, *dlogits, *dz3, *da2, *dz2, *dz1;
-  float *wsl;  // split-K partial slab (B*18432 floats), shared fwd/bwd
-  float *w2t, *w2rot;  // per-batch W2 fragment layouts (18432 floats each)
-  int *yb;
-  unsigned char *pidx, *m2, *m3;
-  double *red_partials, *red_acc;
-};
+__global__ void k_dz2_transpose_mb(const float* __restrict__ dz2, int bs,
+                                   int K, float* __restrict__ dz2t) {
+  long long total = (long long)K * bs * 36864;
+  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+       i < total; i += (long long)gridDim.x * blockDim.x) {
+    long long g = i / 36864;
+    int r = (int)(i % 36864), o = r / 64, co = r % 64;
+    dz2t[i] = dz2[(g * 64 + co) * 576 + o];
+  }
+}
+
+// conv2 backward weights (f32 MFMA): 32x32 (co x n) tiles, K=576
+// staged in TWO 288-deep chunks so the live LDS is 74 KB -> 2
+// blocks/CU (a one-shot 576-deep stage was 149 KB -> 1 block/CU and
+// measured WORSE than the 64-row form).  A = dz2t rows; B = im2col^T.
+// grid = G * 18 (2 co-halves x 9 n-blocks); one accumulator per wave.
+#define MC2FW_LD 289  /* 289 %% 32 = 1 -> conflict-free fragment groups */
+__global__ __launch_bounds__(256)
+void k_conv2_bwd_w_mfma_mb(const float* __restrict__ dz2t,
+                           const float* __restrict__ a1, int bs, int K,
+                           float* __restrict__ slab) {
+  __shared__ float dzl[32 * MC2FW_LD];
+  __shared__ float imt[32 * MC2FW_LD];
+  int blk = blockIdx.x % 18;
+  int ch = blk / 9, nb = blk % 9;
+  long long g = blockIdx.x / 18;
+  const float* dzb = dz2t + g * 36864;   // [o][co] layout
+  const float* a1b = a1 + g * 21632;
+  int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  int il = lane & 15, kc = lane >> 4;
+  int csub = w & 1, nt = w >> 1;
+  f32x4 acc = {0, 0, 0, 0};
+  for (int c = 0; c < 2; ++c) {
+    int obase = c * 288;
+    __syncthreads();
+    for (int i = threadIdx.x; i < 32 * 288; i += 256) {
+      // thread-consecutive co -> 128 B contiguous dz2t reads per o
+      int o = obase + i / 32, co = i % 32;
+      dzl[co * MC2FW_LD + (o - obase)] = dzb[o * 64 + ch * 32 + co];
+    }
+    for (int i = threadIdx.x; i < 32 * 288; i += 256) {
+      int nr = i / 288, o = obase + i % 288;
+      int n = nb * 32 + nr;
+      int ci = n / 9, rem = n % 9, kh = rem / 3, kw = rem % 3;
+      int yy = o / 24, xx = o % 24;
+      imt[nr * MC2FW_LD + (o - obase)] =
+          a1b[ci * 676 + (yy + kh) * 26 + xx + kw];
+    }
+    __syncthreads();
+    #pragma unroll 8
+    for (int k0 = 0; k0 < 288; k0 += 4) {
+      int o = k0 + kc;
+      float a = dzl[(csub * 16 + il) * MC2FW_LD + o];
+      float bv = imt[(nt * 16 + il) * MC2FW_LD + o];
+      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a, bv, acc, 0, 0, 0);
+    }
+  }
+  float* out = slab + g * 18432;
+  int orow = ch * 32 + csub * 16 + (lane >> 4) * 4;
+  #pragma unroll
+  for (int r = 0; r < 4; ++r)
+    out[(orow + r) * 288 + nb * 32 + nt * 16 + il] = acc[r];
+}
+
+__global__ void k_conv2_bwd_w_fold_mb(const float* __restrict__ slab,
+                                      float* __restrict__ grads, long long P,
+                                      long long ow2, int bs, int K) {
+  int per_k = (18432 + FBLK - 1) / FBLK;
+  int k = blockIdx.x / per_k;
+  int i = (blockIdx.x % per_k) * FBLK + threadIdx.x;
+  if (i >= 18432) return;
+  const float* slk = slab + (long long)k * bs * 18432;
+  float s = 0.f;
+  for (int b = 0; b < bs; ++b) s += slk[(long long)b * 18432 + i];
+  grads[(long long)k * P + ow2 + i] = s;
+}
+
+__global__ void k_conv2_bwd_b_mb(const float* __restrict__ dz2,
+                                 float* __restrict__ grads, long long P,
+                                 long long ob2, int bs, int K) {
+  int k = blockIdx.x / 64;
+  int co = blockIdx.x % 64;
+  const float* dzk = dz2 + (long long)k * bs * 36864;
+  float s = 0.f;
+  for (int t = threadIdx.x; t < bs * 576; t += blockDim.x) {
+    int o = t % 576, b = t / 576;
+    s += dzk[((long long)b * 64 + co) * 576 + o];
+  }
+  for (int d = 32; d > 0; d >>= 1) s += __shfl_down(s, d, 64);
+  __shared__ float lds[4];
+  if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float tt = 0.f;
+    for (int q = 0; q < (int)blockDim.x / 64; ++q) tt += lds[q];
+    grads[(long long)k * P + ob2 + co] = tt;
+  }
+}
+
+// conv2 backward data (f32 MFMA): 32-row materialized-im2col tiles
+// (74.9 KB LDS -> 2 blocks/CU), one accumulator per wave (wave w:
+// m-subtile w&1, ci-tile w>>1), B streamed from the per-batch global
+// w2rot layout with lane-contiguous 64 B groups.  grid = G * 22.
+__global__ __launch_bounds__(256)
+void k_conv2_bwd_x_mfma_mb(const float* __restrict__ dz2,
+                           const float* __restrict__ w2rot_stack,
+                           const float* __restrict__ a1, int bs, int K,
+                           float* __restrict__ dz1) {
+  __shared__ float imc[32 * MC2F_LD];
+  long long g = blockIdx.x / 22;
+  int mt = blockIdx.x % 22;
+  int k = (int)(g / bs);
+  const float* dzb = dz2 + g * 36864;
+  const float* w2rot = w2rot_stack + (long long)k * 18432;
+  for (int i = threadIdx.x; i < 32 * 576; i += 256) {
+    int mr = i / 576, kk = i % 576;
+    int m = mt * 32 + mr, p = m / 26, q = m % 26;
+    int co = kk / 9, rem = kk % 9, kh = rem / 3, kw = rem % 3;
+    int y = p - kh, x = q - kw;
+    imc[mr * MC2F_LD + kk] =
+        (m < 676 && y >= 0 && y < 24 && x >= 0 && x < 24)
+            ? dzb[co * 576 + y * 24 + x] : 0.f;
+  }
+  __syncthreads();
+  int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  int il = lane & 15, kc = lane >> 4;
+  int msub = w & 1, nt = w >> 1;
+  f32x4 acc = {0, 0, 0, 0};
+  #pragma unroll 8
+  for (int k0 = 0; k0 < 576; k0 += 4) {
+    int kk = k0 + kc;
+    float a = imc[(msub * 16 + il) * MC2F_LD + kk];
+    float bv = w2rot[(long long)kk * 32 + nt * 16 + il];
+    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a, bv, acc, 0, 0, 0);
+  }
+  int om = mt * 32 + msub * 16 + (lane >> 4) * 4;
+  int ci = nt * 16 + il;
+  #pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    if (om + r >= 676) continue;
+    long long o = (g * 32 + ci) * 676 + om + r;
+    dz1[o] = a1[o] > 0.f ? acc[r] : 0.f;
+  }
+}
+
+__global__ void k_conv1_bwd_w_mb(const float* __restrict__ x,
+                                 const float* __restrict__ dz1,
+                                 float* __restrict__ grads, long long P,
+                                 long long ow1, long long ob1, int bs,
+                                 int K) {
+  int k = blockIdx.x / 32;
+  int co = blockIdx.x % 32;
+  const float* xk = x + (long long)k * bs * 784;
+  const float* dzk = dz1 + (long long)k * bs * 21632;
+  float acc[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+  float accb = 0.f;
+  for (int t = threadIdx.x; t < bs * 676; t += blockDim.x) {
+    int o = t % 676, b = t / 676;
+    int xx = o % 26, yy = o / 26;
+    float d = dzk[((long long)b * 32 + co) * 676 + o];
+    const float* xp = xk + b * 784 + yy * 28 + xx;
+    #pragma unroll
+    for (int kh = 0; kh < 3; ++kh)
+      #pragma unroll
+      for (int kw = 0; kw < 3; ++kw)
+        acc[kh * 3 + kw] = fmaf(xp[kh * 28 + kw], d, acc[kh * 3 + kw]);
+    accb += d;
+  }
+  __shared__ float lds[16 * 10];
+  int n_waves = blockDim.x / 64;
+  int wave = threadIdx.x / 64, lane = threadIdx.x % 64;
+  #pragma unroll
+  for (int kk = 0; kk < 9; ++kk) {
+    float s = acc[kk];
+    for (int d = 32; d > 0; d >>= 1) s += __shfl_down(s, d, 64);
+    if (lane == 0) lds[wave * 10 + kk] = s;
+  }
+  float sb = accb;
+  for (int d = 32; d > 0; d >>= 1) sb += __shfl_down(sb, d, 64);
+  if (lane == 0) lds[wave * 10 + 9] = sb;
+  __syncthreads();
+  if (threadIdx.x < 9) {
+    float s = 0.f;
+    for (int w = 0; w < n_waves; ++w) s += lds[w * 10 + threadIdx.x];
+    grads[(long long)k * P + ow1 + co * 9 + threadIdx.x] = s;
+  }
+  if (threadIdx.x == 9) {
+    float s = 0.f;
+    for (int w = 0; w < n_waves; ++w) s += lds[w * 10 + 9];
+    grads[(long long)k * P + ob1 + co] = s;
+  }
+}
+
+// per-client clip + sufficient stats + SGD over the gradient stacks.
+// Stage 1: per-(k, chunk) partial sum/sumsq -> f64 atomics into acc[2k]
+// (few hundred atomics per client per step).  Stage 2: per-client scale
+// + stats accumulate + SGD in one elementwise pass.
+// one block per (client, contiguous chunk): block-local tree reduce,
+// ONE f64 atomicAdd pair per block (~K * ceil(P/65536) atomics per step)
+#define SUMSQ_CHUNK 32768
+__global__ void k_sumsq_mb(const float* __restrict__ grads, long long P,
+                           int blocks_per_k, double* __restrict__ acc) {
+  int k = blockIdx.x / blocks_per_k;
+  int c = blockIdx.x % blocks_per_k;
+  long long lo = (long long)c * SUMSQ_CHUNK;
+  long long hi = lo + SUMSQ_CHUNK;
+  if (hi > P) hi = P;
+  const float* g = grads + (long long)k * P;
+  // float4 loads + independent accumulator pairs break the dependent
+  // f64-add chain (was ~74 us per step at 190 underfilled blocks)
+  double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
+  double q0 = 0.0, q1 = 0.0, q2 = 0.0, q3 = 0.0;
+  // scalar loads (the k*P segment bases are not 16 B aligned); the win
+  // is the 4 independent f64 accumulator chains
+  long long i = lo + (long long)threadIdx.x * 4;
+  for (; i + 3 < hi; i += (long long)blockDim.x * 4) {
+    double a = g[i], b = g[i + 1], cc = g[i + 2], d = g[i + 3];
+    s0 += a; q0 += a * a;
+    s1 += b; q1 += b * b;
+    s2 += cc; q2 += cc * cc;
+    s3 += d; q3 += d * d;
+  }
+  for (long long j = i; j < hi; ++j) {  // ragged tail (P % 4)
+    double v = (double)g[j];
+    s0 += v; q0 += v * v;
+  }
+  double fs = (s0 + s1) + (s2 + s3);
+  double fq = (q0 + q1) + (q2 + q3);
+  {
+  }
+  for (int d = 32; d > 0; d >>= 1) {
+    fs += __shfl_down(fs, d, 64);
+    fq += __shfl_down(fq, d, 64);
+  }
+  __shared__ double lds[2 * 4];
+  int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  if (lane == 0) { lds[2 * wave] = fs; lds[2 * wave + 1] = fq; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double ts = 0.0, tq = 0.0;
+    for (int w = 0; w < (int)blockDim.x / 64; ++w) {
+      ts += lds[2 * w]; tq += lds[2 * w + 1];
+    }
+    atomicAdd(acc + 2 * k, ts);
+    atomicAdd(acc + 2 * k + 1, tq);
+  }
+}
+
+__global__ void k_clip_sgd_mb(float* __restrict__ params,
+                              float* __restrict__ grads, long long P, int K,
+                              const double* __restrict__ acc, float max_norm,
+                              float eps, const float* __restrict__ lr_t,
+                              float* __restrict__ stats_out) {
+  long long total = (long long)K * P;
+  float lr = lr_t[0];
+  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+       i < total; i += (long long)gridDim.x * blockDim.x) {
+    int k = (int)(i / P);
+    float norm = (float)sqrt(acc[2 * k + 1]);
+    float scale = (max_norm > 0.f && norm > max_norm)
+                      ? max_norm / (norm + eps) : 1.f;
+    float gv = grads[i] * scale;
+    grads[i] = gv;
+    params[i] -= lr * gv;
+  }
+}
+
+// per-client clipped-stats accumulate: stats_out[2k] += scale*sum,
+// stats_out[2k+1] += scale^2*sumsq (one thread per client)
+__global__ void k_stats_mb(const double* __restrict__ acc, int K,
+                           float max_norm, float eps,
+                           float* __restrict__ stats_out) {
+  int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= K) return;
+  float norm = (float)sqrt(acc[2 * k + 1]);
+  float scale = (max_norm > 0.f && norm > max_norm)
+                    ? max_norm / (norm + eps) : 1.f;
+  stats_out[2 * k] += scale * (float)acc[2 * k];
+  stats_out[2 * k + 1] += scale * scale * (float)acc[2 * k + 1];
+}
+
+// weighted pseudo-gradients + deterministic accumulate into round_accum
+__global__ void k_pseudo_grad_mb(float* __restrict__ grads,
+                                 const float* __restrict__ server,
+                                 const float* __restrict__ params,
+                                 const float* __restrict__ weights,
+                                 long long P, int K) {
+  long long total = (long long)K * P;
+  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+       i < total; i += (long long)gridDim.x * blockDim.x) {
+    int k = (int)(i / P);
+    grads[i] = (server[i % P] - params[i]) * weights[k];
+  }
+}
+
+__global__ void k_accum_mb(float* __restrict__ round_accum,
+                           const float* __restrict__ grads, long long P,
+                           int K) {
+  for (long long p = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+       p < P; p += (long long)gridDim.x * blockDim.x) {
+    float s = round_accum[p];
+    for (int k = 0; k < K; ++k) s += grads[(long long)k * P + p];
+    round_accum[p] = s;
+  }
+}
 
 // ---------------------------------------------------------------------------
 // bf16 GEMM kernels (mixed precision: bf16 MFMA inputs at ~13-16x the
@@ -889,30 +984,185 @@ struct CnnWorkspace {
 // SGD step, clip/stats, DP/quant hooks all stay fp32).  The GEMM
 // operands are materialized in LDS as bf16 with k-contiguous rows so
 // each lane's 8-element fragment is ONE 16 B ds_read; row strides are
-// padded so 16-lane fragment groups hit distinct banks.
-// Conversion f32->bf16 happens during LDS staging (round-to-nearest via
-// __bf16 cast) — no global bf16 shadow copies needed.
+// padded so 16-lane fragment groups hit distinct banks.  Conversion
+// f32->bf16 happens during LDS staging (round-to-nearest via __bf16
+// cast); the inner loops read ONLY LDS, so the L2-latency bound of the
+// f32 variants does not apply.
 // ---------------------------------------------------------------------------
-
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 
 __device__ __forceinline__ bf16x8 ld_bf16x8(const __bf16* p) {
   return *reinterpret_cast<const bf16x8*>(p);
 }
 
-// fc1 forward, bf16: z3^T[j,b] partials; split-K 36 (chunk 256 = 8 bf16
-// k-steps).  LDS: W3 chunk [128][256] + a2 chunk [32][256], stride 264.
+// [k][ci][k'=(co,kh,kw)] bf16 layout for the bwd-data B operand (built
+// once per batch into the w2rot_stack buffer reinterpreted as bf16)
+__global__ void k_w2rotbf_mb(const float* __restrict__ params, long long P,
+                             long long ow2, int K,
+                             __bf16* __restrict__ w2rotbf) {
+  long long total = (long long)K * 18432;
+  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+       i < total; i += (long long)gridDim.x * blockDim.x) {
+    int k = (int)(i / 18432), r = (int)(i % 18432);
+    int co = r / 288, rem9 = r % 288;
+    int ci = rem9 / 9, rem = rem9 % 9;
+    w2rotbf[(long long)k * 18432 + (long long)ci * 576 + co * 9 + rem] =
+        (__bf16)params[(long long)k * P + ow2 + r];
+  }
+}
+
+#define MC2_LD 296
+__global__ __launch_bounds__(256)
+void k_conv2_fwd_mfma_mb_bf16(const float* __restrict__ a1,
+                              const float* __restrict__ params, long long P,
+                              long long ow2, long long ob2, int bs, int K,
+                              float* __restrict__ r2) {
+  __shared__ __bf16 imc[64 * MC2_LD];
+  __shared__ __bf16 wb[64 * MC2_LD];
+  long long g = blockIdx.x / 9;
+  int mt = blockIdx.x % 9;
+  int k = (int)(g / bs);
+  const float* a1b = a1 + g * 21632;
+  const float* w2 = params + (long long)k * P + ow2;
+  const float* b2 = params + (long long)k * P + ob2;
+  for (int i = threadIdx.x; i < 64 * 288; i += 256) {
+    int mr = i / 288, kk = i % 288;
+    int m = mt * 64 + mr, yy = m / 24, xx = m % 24;
+    int ci = kk / 9, rem = kk % 9, kh = rem / 3, kw = rem % 3;
+    imc[mr * MC2_LD + kk] = (__bf16)a1b[ci * 676 + (yy + kh) * 26 + xx + kw];
+    wb[mr * MC2_LD + kk] = (__bf16)w2[i];  // mr doubles as co
+  }
+  __syncthreads();
+  int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  int il = lane & 15, kc8 = (lane >> 4) * 8;
+  f32x4 acc[4] = {f32x4{0,0,0,0}, f32x4{0,0,0,0},
+                  f32x4{0,0,0,0}, f32x4{0,0,0,0}};
+  for (int k0 = 0; k0 < 288; k0 += 32) {
+    bf16x8 a = ld_bf16x8(&imc[(w * 16 + il) * MC2_LD + k0 + kc8]);
+    #pragma unroll
+    for (int nt = 0; nt < 4; ++nt) {
+      bf16x8 bv = ld_bf16x8(&wb[(nt * 16 + il) * MC2_LD + k0 + kc8]);
+      acc[nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, bv, acc[nt], 0, 0, 0);
+    }
+  }
+  int om = mt * 64 + w * 16 + (lane >> 4) * 4;
+  #pragma unroll
+  for (int r = 0; r < 4; ++r)
+    #pragma unroll
+    for (int nt = 0; nt < 4; ++nt) {
+      int co = nt * 16 + il;
+      float v = acc[nt][r] + b2[co];
+      r2[(g * 64 + co) * 576 + om + r] = v > 0.f ? v : 0.f;
+    }
+}
+
+#define MC2B_LD 584
+// 32-row m-tiles (imc 37.4 KB -> 4 blocks/CU of 4 waves hide the staging
+// latency that bound the 64-row form to ~340 us); the B operand streams
+// from the pre-built global w2rotbf (18 16-B reads per lane, unrolled).
+// Wave w: m-subtile (w & 1), ci-tile (w >> 1).
+__global__ __launch_bounds__(256)
+void k_conv2_bwd_x_mfma_mb_bf16(const float* __restrict__ dz2,
+                                const __bf16* __restrict__ w2rotbf,
+                                int bs, int K,
+                                const float* __restrict__ a1,
+                                float* __restrict__ dz1) {
+  __shared__ __bf16 imc[32 * MC2B_LD];
+  long long g = blockIdx.x / 22;
+  int mt = blockIdx.x % 22;
+  int k = (int)(g / bs);
+  const float* dzb = dz2 + g * 36864;
+  const __bf16* wtk = w2rotbf + (long long)k * 18432;
+  for (int i = threadIdx.x; i < 32 * 576; i += 256) {
+    int mr = i / 576, kk = i % 576;
+    int m = mt * 32 + mr, p = m / 26, q = m % 26;
+    int co = kk / 9, rem = kk % 9, kh = rem / 3, kw = rem % 3;
+    int y = p - kh, x = q - kw;
+    imc[mr * MC2B_LD + kk] =
+        (__bf16)((m < 676 && y >= 0 && y < 24 && x >= 0 && x < 24)
+                     ? dzb[co * 576 + y * 24 + x] : 0.f);
+  }
+  __syncthreads();
+  int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  int il = lane & 15, kc8 = (lane >> 4) * 8;
+  int msub = w & 1, nt = w >> 1;
+  f32x4 acc = {0, 0, 0, 0};
+  #pragma unroll 3
+  for (int k0 = 0; k0 < 576; k0 += 32) {
+    bf16x8 a = ld_bf16x8(&imc[(msub * 16 + il) * MC2B_LD + k0 + kc8]);
+    bf16x8 bv = ld_bf16x8(&wtk[(long long)(nt * 16 + il) * 576
+                                 + k0 + kc8]);
+    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, bv, acc, 0, 0, 0);
+  }
+  int om = mt * 32 + msub * 16 + (lane >> 4) * 4;
+  int ci = nt * 16 + il;
+  #pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    if (om + r >= 676) continue;
+    long long o = (g * 32 + ci) * 676 + om + r;
+    dz1[o] = a1[o] > 0.f ? acc[r] : 0.f;
+  }
+}
+
+// block = 32 co-rows x 32 n-cols over K=576 (dzb16 37.4 KB + imt
+// 37.4 KB -> 2 blocks/CU); grid = G * 2(co) * 9(n).  Wave w: co-subtile
+// (w & 1), n-subtile (w >> 1).
+__global__ __launch_bounds__(256)
+void k_conv2_bwd_w_mfma_mb_bf16(const float* __restrict__ dz2,
+                                const float* __restrict__ a1, int bs, int K,
+                                float* __restrict__ slab) {
+  __shared__ __bf16 dzb16[32 * MC2B_LD];
+  __shared__ __bf16 imt[32 * MC2B_LD];
+  int blk = blockIdx.x % 18;
+  int ch = blk / 9;         // co half (0: rows 0-31, 1: rows 32-63)
+  int nb = blk % 9;         // 32-col n-block
+  long long g = blockIdx.x / 18;
+  const float* dzb = dz2 + g * 36864 + (long long)ch * 32 * 576;
+  const float* a1b = a1 + g * 21632;
+  for (int i = threadIdx.x; i < 32 * 576; i += 256) {
+    int co = i / 576;
+    dzb16[co * MC2B_LD + (i % 576)] = (__bf16)dzb[i];
+  }
+  for (int i = threadIdx.x; i < 32 * 576; i += 256) {
+    int nr = i / 576, o = i % 576;
+    int n = nb * 32 + nr;
+    int ci = n / 9, rem = n % 9, kh = rem / 3, kw = rem % 3;
+    int yy = o / 24, xx = o % 24;
+    imt[nr * MC2B_LD + o] = (__bf16)a1b[ci * 676 + (yy + kh) * 26 + xx + kw];
+  }
+  __syncthreads();
+  int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  int il = lane & 15, kc8 = (lane >> 4) * 8;
+  int csub = w & 1, nt = w >> 1;
+  f32x4 acc = {0, 0, 0, 0};
+  #pragma unroll 3
+  for (int k0 = 0; k0 < 576; k0 += 32) {
+    bf16x8 a = ld_bf16x8(&dzb16[(csub * 16 + il) * MC2B_LD + k0 + kc8]);
+    bf16x8 bv = ld_bf16x8(&imt[(nt * 16 + il) * MC2B_LD + k0 + kc8]);
+    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, bv, acc, 0, 0, 0);
+  }
+  float* out = slab + g * 18432;
+  int orow = ch * 32 + csub * 16 + (lane >> 4) * 4;
+  #pragma unroll
+  for (int r = 0; r < 4; ++r)
+    out[(orow + r) * 288 + nb * 32 + nt * 16 + il] = acc[r];
+}
+
 #define FC1B_SPLIT 36
 #define FC1B_CH 256
 #define FC1B_LD 264
 __global__ __launch_bounds__(256)
-void k_fc1_fwd_mfma_bf16(const float* __restrict__ a2,
-                         const float* __restrict__ w3, int B,
-                         float* __restrict__ slab) {
+void k_fc1_fwd_mfma_mb_bf16(const float* __restrict__ a2,
+                            const float* __restrict__ params, long long P,
+                            long long ow3, int bs, int K,
+                            float* __restrict__ slab) {
   __shared__ __bf16 lw[128 * FC1B_LD];
   __shared__ __bf16 la[32 * FC1B_LD];
-  int s = blockIdx.x;
+  int k = blockIdx.x / FC1B_SPLIT;
+  int s = blockIdx.x % FC1B_SPLIT;
   int k_base = s * FC1B_CH;
+  const float* w3 = params + (long long)k * P + ow3;
+  const float* a2k = a2 + (long long)k * bs * 9216;
   for (int i = threadIdx.x; i < 128 * FC1B_CH; i += 256) {
     int row = i / FC1B_CH, kk = i % FC1B_CH;
     lw[row * FC1B_LD + kk] = (__bf16)w3[(long long)row * 9216 + k_base + kk];
@@ -920,7 +1170,7 @@ void k_fc1_fwd_mfma_bf16(const float* __restrict__ a2,
   for (int i = threadIdx.x; i < 32 * FC1B_CH; i += 256) {
     int bu = i / FC1B_CH, kk = i % FC1B_CH;
     la[bu * FC1B_LD + kk] =
-        (__bf16)(bu < B ? a2[(long long)bu * 9216 + k_base + kk] : 0.f);
+        (__bf16)(bu < bs ? a2k[(long long)bu * 9216 + k_base + kk] : 0.f);
   }
   __syncthreads();
   int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -937,16 +1187,17 @@ void k_fc1_fwd_mfma_bf16(const float* __restrict__ a2,
       acc[1][u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1v, bv, acc[1][u], 0, 0, 0);
     }
   }
+  float* slk = slab + (long long)k * FC1B_SPLIT * bs * 128;
   #pragma unroll
-  for (int t = 0; t < 2; ++t)
+  for (int tt = 0; tt < 2; ++tt)
     #pragma unroll
     for (int u = 0; u < 2; ++u) {
       int bu = u * 16 + il;
-      if (bu >= B) continue;
-      int j = w * 32 + t * 16 + (lane >> 4) * 4;
+      if (bu >= bs) continue;
+      int j = w * 32 + tt * 16 + (lane >> 4) * 4;
       #pragma unroll
       for (int r = 0; r < 4; ++r)
-        slab[((long long)s * B + bu) * 128 + j + r] = acc[t][u][r];
+        slk[((long long)s * bs + bu) * 128 + j + r] = acc[tt][u][r];
     }
 }
 
@@ -957,175 +1208,26 @@ __global__ void k_fc1_fwd_reduce_bf16(const float* __restrict__ slab,
                                       float* __restrict__ z3,
                                       float* __restrict__ a3,
                                       unsigned char* __restrict__ m3) {
-  int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= B * 128) return;
-  int b = i / 128, j = i % 128;
-  float t = b3[j];
-  for (int s = 0; s < FC1B_SPLIT; ++s)
-    t += slab[((long long)s * B + b) * 128 + j];
-  z3[i] = t;
-  float r = t > 0.f ? t : 0.f;
-  unsigned char keep = 1;
-  if (p2 > 0.f) {
-    hiprandStatePhilox4_32_10_t st;
-    hiprand_init(seed ^ 0x9e3779b97f4a7c15ull, (unsigned long long)i,
-                 offset, &st);
-    keep = hiprand_uniform(&st) >= p2;
-  }
-  m3[i] = keep;
-  a3[i] = keep ? r / (1.f - p2) : 0.f;
+  fc1_reduce_client<FC1B_SPLIT>(slab, b3, B, p2, seed, offset, z3, a3, m3);
 }
 
-// conv2 forward, bf16: im2col A tile [64][288] and W2 [64][288] (both
-// k-contiguous bf16, stride 296) built in LDS per block; 36 bf16 MFMAs
-// per wave replace 288 f32 MFMA issues.
-#define C2_LD 296
-__global__ __launch_bounds__(256)
-void k_conv2_fwd_mfma_bf16(const float* __restrict__ a1,
-                           const float* __restrict__ w2,
-                           const float* __restrict__ b2, int B,
-                           float* __restrict__ r2) {
-  __shared__ __bf16 imc[64 * C2_LD];
-  __shared__ __bf16 wb[64 * C2_LD];
-  int b = blockIdx.x / 9, mt = blockIdx.x % 9;
-  const float* a1b = a1 + (long long)b * 21632;
-  for (int i = threadIdx.x; i < 64 * 288; i += 256) {
-    int mr = i / 288, k = i % 288;
-    int m = mt * 64 + mr, yy = m / 24, xx = m % 24;
-    int ci = k / 9, rem = k % 9, kh = rem / 3, kw = rem % 3;
-    imc[mr * C2_LD + k] = (__bf16)a1b[ci * 676 + (yy + kh) * 26 + xx + kw];
-    wb[mr * C2_LD + k] = (__bf16)w2[i];  // mr doubles as co here
-  }
-  __syncthreads();
-  int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  int il = lane & 15, kc8 = (lane >> 4) * 8;
-  f32x4 acc[4] = {f32x4{0,0,0,0}, f32x4{0,0,0,0},
-                  f32x4{0,0,0,0}, f32x4{0,0,0,0}};
-  for (int k0 = 0; k0 < 288; k0 += 32) {
-    bf16x8 a = ld_bf16x8(&imc[(w * 16 + il) * C2_LD + k0 + kc8]);
-    #pragma unroll
-    for (int nt = 0; nt < 4; ++nt) {
-      bf16x8 bv = ld_bf16x8(&wb[(nt * 16 + il) * C2_LD + k0 + kc8]);
-      acc[nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, bv, acc[nt], 0, 0, 0);
-    }
-  }
-  int om = mt * 64 + w * 16 + (lane >> 4) * 4;
-  #pragma unroll
-  for (int r = 0; r < 4; ++r)
-    #pragma unroll
-    for (int nt = 0; nt < 4; ++nt) {
-      int co = nt * 16 + il;
-      float v = acc[nt][r] + b2[co];
-      r2[((long long)b * 64 + co) * 576 + om + r] = v > 0.f ? v : 0.f;
-    }
+__global__ void k_fc1_fwd_reduce_mb_bf16(const float* __restrict__ slab,
+                                         const float* __restrict__ params,
+                                         long long P, long long ob3, int bs,
+                                         int K, float p2,
+                                         const long long* __restrict__ seeds,
+                                         unsigned long long offset,
+                                         float* __restrict__ z3,
+                                         float* __restrict__ a3,
+                                         unsigned char* __restrict__ m3) {
+  fc1_reduce_stack<FC1B_SPLIT>(slab, params, P, ob3, bs, K, p2, seeds,
+                               offset, z3, a3, m3);
 }
 
-// conv2 backward-data, bf16: padded-im2col A tile [64][576] of dz2 plus
-// W2^T-per-ci tile [32][576] (k=(co,kh,kw) contiguous), stride 584.
-#define C2B_LD 584
-__global__ __launch_bounds__(256)
-void k_conv2_bwd_x_mfma_bf16(const float* __restrict__ dz2,
-                             const float* __restrict__ w2,
-                             const float* __restrict__ a1, int B,
-                             float* __restrict__ dz1) {
-  __shared__ __bf16 imc[64 * C2B_LD];   // 74.8 KB
-  __shared__ __bf16 wt[32 * C2B_LD];    // 37.4 KB
-  int b = blockIdx.x / 11, mt = blockIdx.x % 11;
-  const float* dzb = dz2 + (long long)b * 36864;
-  for (int i = threadIdx.x; i < 64 * 576; i += 256) {
-    int mr = i / 576, k = i % 576;
-    int m = mt * 64 + mr, p = m / 26, q = m % 26;
-    int co = k / 9, rem = k % 9, kh = rem / 3, kw = rem % 3;
-    int y = p - kh, x = q - kw;
-    imc[mr * C2B_LD + k] =
-        (__bf16)((m < 676 && y >= 0 && y < 24 && x >= 0 && x < 24)
-                     ? dzb[co * 576 + y * 24 + x] : 0.f);
-  }
-  for (int i = threadIdx.x; i < 32 * 576; i += 256) {
-    int ci = i / 576, k = i % 576;
-    int co = k / 9, rem = k % 9;
-    wt[ci * C2B_LD + k] = (__bf16)w2[(long long)co * 288 + ci * 9 + rem];
-  }
-  __syncthreads();
-  int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  int il = lane & 15, kc8 = (lane >> 4) * 8;
-  f32x4 acc[2] = {f32x4{0,0,0,0}, f32x4{0,0,0,0}};
-  for (int k0 = 0; k0 < 576; k0 += 32) {
-    bf16x8 a = ld_bf16x8(&imc[(w * 16 + il) * C2B_LD + k0 + kc8]);
-    #pragma unroll
-    for (int nt = 0; nt < 2; ++nt) {
-      bf16x8 bv = ld_bf16x8(&wt[(nt * 16 + il) * C2B_LD + k0 + kc8]);
-      acc[nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, bv, acc[nt], 0, 0, 0);
-    }
-  }
-  int om = mt * 64 + w * 16 + (lane >> 4) * 4;
-  #pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    if (om + r >= 676) continue;
-    #pragma unroll
-    for (int nt = 0; nt < 2; ++nt) {
-      int ci = nt * 16 + il;
-      long long o = ((long long)b * 32 + ci) * 676 + om + r;
-      dz1[o] = a1[o] > 0.f ? acc[nt][r] : 0.f;
-    }
-  }
-}
-
-// conv2 backward-weight, bf16: dz2[b] as bf16 [64][576] (A, k=o
-// contiguous) + im2col^T tile [48][576] of a1 (B); per-b slabs folded
-// deterministically as in the f32 path.
-__global__ __launch_bounds__(256)
-void k_conv2_bwd_w_mfma_bf16(const float* __restrict__ dz2,
-                             const float* __restrict__ a1, int B,
-                             float* __restrict__ slab) {
-  __shared__ __bf16 dzb16[64 * C2B_LD];  // 74.8 KB
-  __shared__ __bf16 imt[48 * C2B_LD];    // 56.1 KB
-  int nb = blockIdx.x % 6, b = blockIdx.x / 6;
-  const float* dzb = dz2 + (long long)b * 36864;
-  const float* a1b = a1 + (long long)b * 21632;
-  for (int i = threadIdx.x; i < 64 * 576; i += 256) {
-    int co = i / 576, o = i % 576;
-    dzb16[co * C2B_LD + o] = (__bf16)dzb[i];
-    (void)o;
-  }
-  for (int i = threadIdx.x; i < 48 * 576; i += 256) {
-    int nr = i / 576, o = i % 576;
-    int n = nb * 48 + nr;
-    int ci = n / 9, rem = n % 9, kh = rem / 3, kw = rem % 3;
-    int yy = o / 24, xx = o % 24;
-    imt[nr * C2B_LD + o] = (__bf16)a1b[ci * 676 + (yy + kh) * 26 + xx + kw];
-  }
-  __syncthreads();
-  int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  int il = lane & 15, kc8 = (lane >> 4) * 8;
-  f32x4 acc[3] = {f32x4{0,0,0,0}, f32x4{0,0,0,0}, f32x4{0,0,0,0}};
-  for (int k0 = 0; k0 < 576; k0 += 32) {
-    bf16x8 a = ld_bf16x8(&dzb16[(w * 16 + il) * C2B_LD + k0 + kc8]);
-    #pragma unroll
-    for (int nt = 0; nt < 3; ++nt) {
-      bf16x8 bv = ld_bf16x8(&imt[(nt * 16 + il) * C2B_LD + k0 + kc8]);
-      acc[nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, bv, acc[nt], 0, 0, 0);
-    }
-  }
-  float* out = slab + (long long)b * 18432;
-  int orow = w * 16 + (lane >> 4) * 4;
-  #pragma unroll
-  for (int r = 0; r < 4; ++r)
-    #pragma unroll
-    for (int nt = 0; nt < 3; ++nt)
-      out[(orow + r) * 288 + nb * 48 + nt * 16 + il] = acc[nt][r];
-}
-
-
-// ---------------------------------------------------------------------------
 // bf16 MFMA probe: one v_mfma_f32_16x16x32_bf16 with the documented
 // fragment maps (A[i=l&15][k=(l>>4)*8+e], B[k=(l>>4)*8+e][j=l&15],
-// D[row=(l>>4)*4+r][col=l&15]) — the numerics test pins the layout
-// before the bf16 kernels build on it.
-// ---------------------------------------------------------------------------
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4_;
-
+// D[row=(l>>4)*4+r][col=l&15]) — the numerics test pins the layout the
+// bf16 kernels build on.
 __global__ void k_mfma_bf16_probe(const __bf16* __restrict__ A,   // [16][32]
                                   const __bf16* __restrict__ B,   // [32][16]
                                   float* __restrict__ D) {        // [16][16]
@@ -1144,51 +1246,16 @@ __global__ void k_mfma_bf16_probe(const __bf16* __restrict__ A,   // [16][32]
     D[((l >> 4) * 4 + r) * 16 + (l & 15)] = acc[r];
 }
 
-extern "C" void launch_fc1_fwd_mfma_bf16(const float* a2, const float* w3,
-                              const float* b3, int B, float p2,
-                              unsigned long long seed,
-                              unsigned long long offset, float* slab,
-                              float* z3, float* a3, unsigned char* m3,
-                              hipStream_t s) {
-  hipLaunchKernelGGL(k_fc1_fwd_mfma_bf16, dim3(FC1B_SPLIT), dim3(FBLK), 0, s,
-                     a2, w3, B, slab);
-  hipLaunchKernelGGL(k_fc1_fwd_reduce_bf16, dim3((B * 128 + FBLK - 1) / FBLK),
-                     dim3(FBLK), 0, s, slab, b3, B, p2, seed, offset,
-                     z3, a3, m3);
-}
-extern "C" void launch_conv2_fwd_mfma_bf16(const float* a1, const float* w2,
-                                const float* b2, int B, float* r2,
-                                hipStream_t s) {
-  hipLaunchKernelGGL(k_conv2_fwd_mfma_bf16, dim3(B * 9), dim3(FBLK), 0, s,
-                     a1, w2, b2, B, r2);
-}
-extern "C" void launch_conv2_bwd_x_mfma_bf16(const float* dz2, const float* w2,
-                                  const float* a1, int B, float* dz1,
-                                  hipStream_t s) {
-  hipLaunchKernelGGL(k_conv2_bwd_x_mfma_bf16, dim3(B * 11), dim3(FBLK), 0, s,
-                     dz2, w2, a1, B, dz1);
-}
-extern "C" void launch_conv2_bwd_w_mfma_bf16(const float* dz2, const float* a1, int B,
-                                  float* slab, float* dw2, float* db2,
-                                  hipStream_t s) {
-  hipLaunchKernelGGL(k_conv2_bwd_w_mfma_bf16, dim3(6 * B), dim3(FBLK), 0, s,
-                     dz2, a1, B, slab);
-  hipLaunchKernelGGL(k_conv2_bwd_w_fold, dim3((18432 + FBLK - 1) / FBLK),
-                     dim3(FBLK), 0, s, slab, B, dw2);
-  hipLaunchKernelGGL(k_conv2_bwd_b, dim3(64), dim3(FBLK), 0, s, dz2, B, db2);
-}
-extern "C" void launch_mfma_bf16_probe(const void* A, const void* B, float* D,
-                                       hipStream_t s) {
-  hipLaunchKernelGGL(k_mfma_bf16_probe, dim3(1), dim3(64), 0, s,
-                     (const __bf16*)A, (const __bf16*)B, D);
-}
 
+// ---------------------------------------------------------------------------
+// per-client epoch driver: loops every batch of ONE client's local epoch,
+// launching the stacked kernels at K = 1 (bs := this batch's row count,
+// the client's arena as the stack) + clip-stats + SGD via flat_ops.hip.
+// ---------------------------------------------------------------------------
 
 // CNN_EPOCH_DEBUG=1: synchronize + check after every launch so a device
 // fault names the kernel that raised it (diagnostics only — the hot path
 // never syncs)
-#include <cstdio>
-#include <cstdlib>
 #define EPOCH_CHK(name)                                                    \
   do {                                                                     \
     if (epoch_dbg) {                                                       \
@@ -1208,51 +1275,58 @@ extern "C" void launch_cnn_epoch(
     long long n, int bs, int C, float* params, float* grads,
     CnnWorkspace ws, const float* lr_t, float max_norm, float p1, float p2,
     float* stats_acc, float* loss_acc, unsigned long long seed,
-    hipStream_t s, long long row_base = 0, int use_bf16 = 0) {
+    hipStream_t s, long long row_base, int use_bf16) {
   static const bool epoch_dbg = getenv("CNN_EPOCH_DEBUG") != nullptr;
   CnnOffsets o = cnn_offsets(C);
+  long long P = o.total;
+  const int K = 1;
   int n_batches = (int)((n + bs - 1) / bs);
   for (int it = 0; it < n_batches; ++it) {
     long long start = (long long)it * bs;
     int B = (int)((start + bs <= n) ? bs : (n - start));
     unsigned long long off = (unsigned long long)it;
-    int g1 = (B * 784 + FBLK - 1) / FBLK;
-    hipLaunchKernelGGL(k_gather_batch, dim3(g1), dim3(FBLK), 0, s,
-                       shard_x, shard_y, order, start, row_base, B,
-                       ws.xb, ws.yb);
+    hipLaunchKernelGGL(k_gather_batch, dim3((B * 784 + FBLK - 1) / FBLK),
+                       dim3(FBLK), 0, s, shard_x, shard_y, order, start,
+                       row_base, B, ws.xb, ws.yb);
     EPOCH_CHK("k_gather_batch");
-    hipLaunchKernelGGL(k_conv1_fwd, dim3((B * 21632 + FBLK - 1) / FBLK),
-                       dim3(FBLK), 0, s, ws.xb, params + o.w1, params + o.b1,
-                       B, ws.a1);
-    EPOCH_CHK("k_conv1_fwd");
+    hipLaunchKernelGGL(k_conv1_fwd_mb, dim3((B * 21632 + FBLK - 1) / FBLK),
+                       dim3(FBLK), 0, s, ws.xb, params, P, o.w1, o.b1, B, K,
+                       ws.a1);
+    EPOCH_CHK("k_conv1_fwd_mb");
     if (use_bf16) {
-      // bf16 kernels read w2 directly (LDS staging converts)
-      hipLaunchKernelGGL(k_conv2_fwd_mfma_bf16, dim3(B * 9), dim3(FBLK),
-                         0, s, ws.a1, params + o.w2, params + o.b2, B, ws.r2);
+      // bf16 kernels read w2 directly (LDS staging converts); bwd-data
+      // wants its own [ci][k'] bf16 layout, which fits in ws.w2rot
+      hipLaunchKernelGGL(k_w2rotbf_mb, dim3((18432 + FBLK - 1) / FBLK),
+                         dim3(FBLK), 0, s, params, P, o.w2, K,
+                         reinterpret_cast<__bf16*>(ws.w2rot));
+      EPOCH_CHK("k_w2rotbf_mb");
+      hipLaunchKernelGGL(k_conv2_fwd_mfma_mb_bf16, dim3(B * 9), dim3(FBLK),
+                         0, s, ws.a1, params, P, o.w2, o.b2, B, K, ws.r2);
     } else {
-      hipLaunchKernelGGL(k_w2_layouts, dim3((18432 + FBLK - 1) / FBLK),
-                         dim3(FBLK), 0, s, params + o.w2, ws.w2t, ws.w2rot);
-      EPOCH_CHK("k_w2_layouts");
-      hipLaunchKernelGGL(k_conv2_fwd_mfma, dim3(B * 9), dim3(FBLK),
-                         0, s, ws.a1, ws.w2t, params + o.b2, B, ws.r2);
+      hipLaunchKernelGGL(k_w2_layouts_mb, dim3((18432 + FBLK - 1) / FBLK),
+                         dim3(FBLK), 0, s, params, P, o.w2, K, ws.w2t,
+                         ws.w2rot);
+      EPOCH_CHK("k_w2_layouts_mb");
+      hipLaunchKernelGGL(k_conv2_fwd_mfma_mb, dim3(B * 9), dim3(FBLK), 0, s,
+                         ws.a1, ws.w2t, params, P, o.b2, B, K, ws.r2);
     }
-    EPOCH_CHK("k_conv2_fwd_mfma");
+    EPOCH_CHK("k_conv2_fwd_mfma_mb");
     hipLaunchKernelGGL(k_pool_drop_fwd, dim3((B * 9216 + FBLK - 1) / FBLK),
                        dim3(FBLK), 0, s, ws.r2, B, p1, seed, off, ws.a2,
                        ws.pidx, ws.m2);
     EPOCH_CHK("k_pool_drop_fwd");
     if (use_bf16) {
-      hipLaunchKernelGGL(k_fc1_fwd_mfma_bf16, dim3(FC1B_SPLIT), dim3(FBLK),
-                         0, s, ws.a2, params + o.w3, B, ws.wsl);
-      EPOCH_CHK("k_fc1_fwd_mfma_bf16");
+      hipLaunchKernelGGL(k_fc1_fwd_mfma_mb_bf16, dim3(FC1B_SPLIT), dim3(FBLK),
+                         0, s, ws.a2, params, P, o.w3, B, K, ws.wsl);
+      EPOCH_CHK("k_fc1_fwd_mfma_mb_bf16");
       hipLaunchKernelGGL(k_fc1_fwd_reduce_bf16,
                          dim3((B * 128 + FBLK - 1) / FBLK),
                          dim3(FBLK), 0, s, ws.wsl, params + o.b3, B, p2, seed,
                          off, ws.z3, ws.a3, ws.m3);
     } else {
-      hipLaunchKernelGGL(k_fc1_fwd_mfma, dim3(FC1_SPLIT), dim3(FBLK), 0, s,
-                         ws.a2, params + o.w3, B, ws.wsl);
-      EPOCH_CHK("k_fc1_fwd_mfma");
+      hipLaunchKernelGGL(k_fc1_fwd_mfma_mb, dim3(FC1_SPLIT), dim3(FBLK), 0, s,
+                         ws.a2, params, P, o.w3, B, K, ws.wsl);
+      EPOCH_CHK("k_fc1_fwd_mfma_mb");
       hipLaunchKernelGGL(k_fc1_fwd_reduce, dim3((B * 128 + FBLK - 1) / FBLK),
                          dim3(FBLK), 0, s, ws.wsl, params + o.b3, B, p2, seed,
                          off, ws.z3, ws.a3, ws.m3);
@@ -1262,54 +1336,58 @@ extern "C" void launch_cnn_epoch(
                        C * (int)sizeof(float), s, ws.a3, params + o.w4,
                        params + o.b4, ws.yb, B, C, ws.dlogits, loss_acc);
     EPOCH_CHK("k_fc2_loss_fwd");
-    hipLaunchKernelGGL(k_fc2_bwd_w, dim3((C * 128 + FBLK - 1) / FBLK),
-                       dim3(FBLK), 0, s, ws.dlogits, ws.a3, B, C,
-                       grads + o.w4, grads + o.b4);
-    EPOCH_CHK("k_fc2_bwd_w");
-    hipLaunchKernelGGL(k_fc2_bwd_x, dim3((B * 128 + FBLK - 1) / FBLK),
-                       dim3(FBLK), 0, s, ws.dlogits, params + o.w4, ws.z3,
-                       ws.m3, B, C, p2, ws.dz3);
-    EPOCH_CHK("k_fc2_bwd_x");
-    hipLaunchKernelGGL(k_fc1_bwd_w_mfma, dim3(144), dim3(FBLK), 0, s,
-                       ws.dz3, ws.a2, B, grads + o.w3);
-    EPOCH_CHK("k_fc1_bwd_w_mfma");
-    hipLaunchKernelGGL(k_fc1_bwd_b, dim3(1), dim3(128), 0, s,
-                       ws.dz3, B, grads + o.b3);
-    EPOCH_CHK("k_fc1_bwd_b");
-    hipLaunchKernelGGL(k_fc1_bwd_x_mfma, dim3(144), dim3(FBLK), 0, s,
-                       ws.dz3, params + o.w3, B, ws.da2);
-    EPOCH_CHK("k_fc1_bwd_x_mfma");
-    hipLaunchKernelGGL(k_pool_drop_bwd, dim3((B * 9216 + FBLK - 1) / FBLK),
-                       dim3(FBLK), 0, s, ws.da2, ws.pidx, ws.m2, ws.r2, B,
+    hipLaunchKernelGGL(k_fc2_bwd_w_mb, dim3((C * 128 + FBLK - 1) / FBLK),
+                       dim3(FBLK), 0, s, ws.dlogits, ws.a3, grads, P, o.w4,
+                       o.b4, B, K, C);
+    EPOCH_CHK("k_fc2_bwd_w_mb");
+    hipLaunchKernelGGL(k_fc2_bwd_x_mb, dim3((B * 128 + FBLK - 1) / FBLK),
+                       dim3(FBLK), 0, s, ws.dlogits, params, P, o.w4, ws.z3,
+                       ws.m3, B, K, C, p2, ws.dz3);
+    EPOCH_CHK("k_fc2_bwd_x_mb");
+    hipLaunchKernelGGL(k_fc1_bwd_w_mfma_mb, dim3(144), dim3(FBLK), 0, s,
+                       ws.dz3, ws.a2, grads, P, o.w3, B, K);
+    EPOCH_CHK("k_fc1_bwd_w_mfma_mb");
+    hipLaunchKernelGGL(k_fc1_bwd_b_mb, dim3(K), dim3(128), 0, s,
+                       ws.dz3, grads, P, o.b3, B, K);
+    EPOCH_CHK("k_fc1_bwd_b_mb");
+    hipLaunchKernelGGL(k_fc1_bwd_x_mfma_mb, dim3(144), dim3(FBLK), 0, s,
+                       ws.dz3, params, P, o.w3, B, K, ws.da2);
+    EPOCH_CHK("k_fc1_bwd_x_mfma_mb");
+    hipLaunchKernelGGL(k_pool_drop_bwd_mb, dim3((B * 9216 + FBLK - 1) / FBLK),
+                       dim3(FBLK), 0, s, ws.da2, ws.pidx, ws.m2, ws.r2, B, K,
                        p1, ws.dz2);
-    EPOCH_CHK("k_pool_drop_bwd");
+    EPOCH_CHK("k_pool_drop_bwd_mb");
     if (use_bf16) {
-      hipLaunchKernelGGL(k_conv2_bwd_w_mfma_bf16, dim3(6 * B), dim3(FBLK),
-                         0, s, ws.dz2, ws.a1, B, ws.wsl);
+      hipLaunchKernelGGL(k_conv2_bwd_w_mfma_mb_bf16, dim3(18 * B), dim3(FBLK),
+                         0, s, ws.dz2, ws.a1, B, K, ws.wsl);
     } else {
-      hipLaunchKernelGGL(k_dz2_transpose, dim3((B * 36864 + FBLK - 1) / FBLK),
-                         dim3(FBLK), 0, s, ws.dz2, B, ws.r2);
-      EPOCH_CHK("k_dz2_transpose");
-      hipLaunchKernelGGL(k_conv2_bwd_w_mfma, dim3(6 * B), dim3(FBLK), 0, s,
-                         ws.r2, ws.a1, B, ws.wsl);
+      // dz2 transposed into ws.r2, which is free after pool_drop_bwd
+      hipLaunchKernelGGL(k_dz2_transpose_mb,
+                         dim3((B * 36864 + FBLK - 1) / FBLK), dim3(FBLK), 0,
+                         s, ws.dz2, B, K, ws.r2);
+      EPOCH_CHK("k_dz2_transpose_mb");
+      hipLaunchKernelGGL(k_conv2_bwd_w_mfma_mb, dim3(18 * B), dim3(FBLK), 0,
+                         s, ws.r2, ws.a1, B, K, ws.wsl);
     }
-    EPOCH_CHK("k_conv2_bwd_w_mfma");
-    hipLaunchKernelGGL(k_conv2_bwd_w_fold, dim3((18432 + FBLK - 1) / FBLK),
-                       dim3(FBLK), 0, s, ws.wsl, B, grads + o.w2);
-    EPOCH_CHK("k_conv2_bwd_w_fold");
-    hipLaunchKernelGGL(k_conv2_bwd_b, dim3(64), dim3(FBLK), 0, s,
-                       ws.dz2, B, grads + o.b2);
-    EPOCH_CHK("k_conv2_bwd_b");
+    EPOCH_CHK("k_conv2_bwd_w_mfma_mb");
+    hipLaunchKernelGGL(k_conv2_bwd_w_fold_mb, dim3((18432 + FBLK - 1) / FBLK),
+                       dim3(FBLK), 0, s, ws.wsl, grads, P, o.w2, B, K);
+    EPOCH_CHK("k_conv2_bwd_w_fold_mb");
+    hipLaunchKernelGGL(k_conv2_bwd_b_mb, dim3(64), dim3(FBLK), 0, s,
+                       ws.dz2, grads, P, o.b2, B, K);
+    EPOCH_CHK("k_conv2_bwd_b_mb");
     if (use_bf16)
-      hipLaunchKernelGGL(k_conv2_bwd_x_mfma_bf16, dim3(B * 11), dim3(FBLK),
-                         0, s, ws.dz2, params + o.w2, ws.a1, B, ws.dz1);
+      hipLaunchKernelGGL(k_conv2_bwd_x_mfma_mb_bf16, dim3(B * 22), dim3(FBLK),
+                         0, s, ws.dz2,
+                         reinterpret_cast<const __bf16*>(ws.w2rot), B, K,
+                         ws.a1, ws.dz1);
     else
-      hipLaunchKernelGGL(k_conv2_bwd_x_mfma, dim3(B * 11), dim3(FBLK),
-                         0, s, ws.dz2, ws.w2rot, ws.a1, B, ws.dz1);
-    EPOCH_CHK("k_conv2_bwd_x_mfma");
-    hipLaunchKernelGGL(k_conv1_bwd_w, dim3(32), dim3(1024), 0, s,
-                       ws.xb, ws.dz1, B, grads + o.w1, grads + o.b1);
-    EPOCH_CHK("k_conv1_bwd_w");
+      hipLaunchKernelGGL(k_conv2_bwd_x_mfma_mb, dim3(B * 22), dim3(FBLK),
+                         0, s, ws.dz2, ws.w2rot, ws.a1, B, K, ws.dz1);
+    EPOCH_CHK("k_conv2_bwd_x_mfma_mb");
+    hipLaunchKernelGGL(k_conv1_bwd_w_mb, dim3(32), dim3(1024), 0, s,
+                       ws.xb, ws.dz1, grads, P, o.w1, o.b1, B, K);
+    EPOCH_CHK("k_conv1_bwd_w_mb");
     // fused clip + sufficient stats + SGD on the whole arena
     hipMemsetAsync(ws.red_acc, 0, 2 * sizeof(double), s);
     launch_sum_sumsq2(grads, o.total, ws.red_partials, ws.red_acc, s);
@@ -1324,20 +1402,16 @@ extern "C" void launch_cnn_epoch(
 }
 
 // ---------------------------------------------------------------------------
-// WHOLE-ROUND driver: trains K clients back-to-back in one host call —
-// per client: copy-in server weights, run the fused epoch, write the
-// weighted pseudo-gradient, accumulate into the round buffer.  Per-client
-// losses/stats land in slots of loss_out[K] / stats_out[K*2].
+// per-client WHOLE-ROUND driver: trains K clients back-to-back in one
+// host call — per client: copy-in server weights, run the fused epoch,
+// write the weighted pseudo-gradient, accumulate into the round buffer.
+// Per-client losses/stats land in slots of loss_out[K] / stats_out[K*2].
 // ---------------------------------------------------------------------------
 extern "C" void launch_cnn_round(
-    const float* shard_x, const long long* shard_y,
-    const long long* orders,            // concatenated per-client shuffles
-    const long long* row_bases,         // HOST: K shard row offsets
-    const long long* order_offs,        // HOST: K offsets into `orders`
-    const long long* counts,            // HOST: K sample counts
-    const float* weights,               // HOST: K aggregation weights
-    const unsigned long long* seeds,    // HOST: K dropout seeds
-    int K, int bs, int C,
+    const float* shard_x, const long long* shard_y, const long long* orders,
+    const long long* row_bases, const long long* order_offs,
+    const long long* counts, const float* weights,
+    const unsigned long long* seeds, int K, int bs, int C,
     const float* server_params, float* params, float* grads,
     float* round_accum, CnnWorkspace ws, const float* lr_t, float max_norm,
     float p1, float p2, float* stats_out, float* loss_out,
@@ -1360,56 +1434,297 @@ extern "C" void launch_cnn_round(
 }
 
 // ---------------------------------------------------------------------------
-// debug/test launchers for the MFMA kernels (numerics tests call these
-// one-by-one against torch references — tests/test_mfma_gpu.py)
+// mega driver: one launch set per batch-step for ALL K clients
 // ---------------------------------------------------------------------------
+extern "C" void launch_cnn_round_mega(
+    const float* shard_x, const long long* shard_y,
+    const long long* orders_dev,
+    const long long* row_bases_dev, const long long* order_offs_dev,
+    const long long* counts_dev, const long long* counts_host,
+    const float* weights_dev, const long long* seeds_dev,
+    int K, int bs, int C,
+    const float* server_params, float* params_stack, float* grads_stack,
+    float* round_accum,
+    float* xb, float* a1, float* r2, float* a2, float* z3, float* a3,
+    float* dlogits, float* dz3, float* da2, float* dz2, float* dz1,
+    float* w2t_stack, float* w2rot_stack, float* slab,
+    int* yb, unsigned char* pidx, unsigned char* m2, unsigned char* m3,
+    double* acc2k,
+    const float* lr_t, float max_norm, float p1, float p2,
+    float* stats_out, float* loss_out, hipStream_t s, int use_bf16) {
+  CnnOffsets o = cnn_offsets(C);
+  long long P = o.total;
+  int G = K * bs;
+  int max_batches = 0;
+  for (int k = 0; k < K; ++k) {
+    int nb = (int)((counts_host[k] + bs - 1) / bs);
+    if (nb > max_batches) max_batches = nb;
+  }
+  long long kp = (long long)K * P;
+  int gkp = (int)((kp + FBLK - 1) / FBLK); if (gkp > 4096) gkp = 4096;
+  int gp = (int)((P + FBLK - 1) / FBLK); if (gp > 2048) gp = 2048;
+  hipLaunchKernelGGL(k_copy_stack, dim3(gkp), dim3(FBLK), 0, s,
+                     params_stack, server_params, P, K);
+  for (int t = 0; t < max_batches; ++t) {
+    unsigned long long off = (unsigned long long)t;
+    hipLaunchKernelGGL(k_gather_mb, dim3((G * 784 + FBLK - 1) / FBLK),
+                       dim3(FBLK), 0, s, shard_x, shard_y, orders_dev,
+                       row_bases_dev, order_offs_dev, counts_dev, t, bs, K,
+                       xb, yb);
+    hipLaunchKernelGGL(k_conv1_fwd_mb,
+                       dim3((int)(((long long)G * 21632 + FBLK - 1) / FBLK)),
+                       dim3(FBLK), 0, s, xb, params_stack, P, o.w1, o.b1,
+                       bs, K, a1);
+    if (use_bf16) {
+      hipLaunchKernelGGL(k_w2rotbf_mb,
+                         dim3((int)(((long long)K * 18432 + FBLK - 1) / FBLK)),
+                         dim3(FBLK), 0, s, params_stack, P, o.w2, K,
+                         reinterpret_cast<__bf16*>(w2rot_stack));
+      hipLaunchKernelGGL(k_conv2_fwd_mfma_mb_bf16, dim3(G * 9), dim3(FBLK),
+                         0, s, a1, params_stack, P, o.w2, o.b2, bs, K, r2);
+    } else {
+      hipLaunchKernelGGL(k_w2_layouts_mb,
+                         dim3((int)(((long long)K * 18432 + FBLK - 1) / FBLK)),
+                         dim3(FBLK), 0, s, params_stack, P, o.w2, K,
+                         w2t_stack, w2rot_stack);
+      hipLaunchKernelGGL(k_conv2_fwd_mfma_mb, dim3(G * 9), dim3(FBLK), 0, s,
+                         a1, w2t_stack, params_stack, P, o.b2, bs, K, r2);
+    }
+    hipLaunchKernelGGL(k_pool_drop_fwd_mb,
+                       dim3((int)(((long long)G * 9216 + FBLK - 1) / FBLK)),
+                       dim3(FBLK), 0, s, r2, bs, K, p1, seeds_dev, off,
+                       a2, pidx, m2);
+    if (use_bf16) {
+      hipLaunchKernelGGL(k_fc1_fwd_mfma_mb_bf16, dim3(K * 36), dim3(FBLK),
+                         0, s, a2, params_stack, P, o.w3, bs, K, slab);
+      hipLaunchKernelGGL(k_fc1_fwd_reduce_mb_bf16,
+                         dim3((int)(((long long)G * 128 + FBLK - 1) / FBLK)),
+                         dim3(FBLK), 0, s, slab, params_stack, P, o.b3, bs,
+                         K, p2, seeds_dev, off, z3, a3, m3);
+    } else {
+      hipLaunchKernelGGL(k_fc1_fwd_mfma_mb, dim3(K * FC1_SPLIT), dim3(FBLK),
+                         0, s, a2, params_stack, P, o.w3, bs, K, slab);
+      hipLaunchKernelGGL(k_fc1_fwd_reduce_mb,
+                         dim3((int)(((long long)G * 128 + FBLK - 1) / FBLK)),
+                         dim3(FBLK), 0, s, slab, params_stack, P, o.b3, bs,
+                         K, p2, seeds_dev, off, z3, a3, m3);
+    }
+    hipLaunchKernelGGL(k_fc2_loss_fwd_mb, dim3(G), dim3(FBLK),
+                       C * (int)sizeof(float), s, a3, params_stack, P, o.w4,
+                       o.b4, counts_dev, t, bs, K, C, yb, dlogits, loss_out);
+    int perk_fc2 = (C * 128 + FBLK - 1) / FBLK;
+    hipLaunchKernelGGL(k_fc2_bwd_w_mb, dim3(K * perk_fc2), dim3(FBLK), 0, s,
+                       dlogits, a3, grads_stack, P, o.w4, o.b4, bs, K, C);
+    hipLaunchKernelGGL(k_fc2_bwd_x_mb,
+                       dim3((int)(((long long)G * 128 + FBLK - 1) / FBLK)),
+                       dim3(FBLK), 0, s, dlogits, params_stack, P, o.w4,
+                       z3, m3, bs, K, C, p2, dz3);
+    hipLaunchKernelGGL(k_fc1_bwd_w_mfma_mb, dim3(K * 144), dim3(FBLK), 0, s,
+                       dz3, a2, grads_stack, P, o.w3, bs, K);
+    hipLaunchKernelGGL(k_fc1_bwd_b_mb, dim3(K), dim3(128), 0, s,
+                       dz3, grads_stack, P, o.b3, bs, K);
+    hipLaunchKernelGGL(k_fc1_bwd_x_mfma_mb, dim3(K * 144), dim3(FBLK), 0, s,
+                       dz3, params_stack, P, o.w3, bs, K, da2);
+    hipLaunchKernelGGL(k_pool_drop_bwd_mb,
+                       dim3((int)(((long long)G * 9216 + FBLK - 1) / FBLK)),
+                       dim3(FBLK), 0, s, da2, pidx, m2, r2, bs, K, p1, dz2);
+    if (use_bf16) {
+      hipLaunchKernelGGL(k_conv2_bwd_w_mfma_mb_bf16, dim3(18 * G), dim3(FBLK),
+                         0, s, dz2, a1, bs, K, slab);
+    } else {
+      hipLaunchKernelGGL(k_dz2_transpose_mb,
+                         dim3((int)(((long long)G * 36864 + FBLK - 1) / FBLK)),
+                         dim3(FBLK), 0, s, dz2, bs, K, r2);  // r2 free now
+      hipLaunchKernelGGL(k_conv2_bwd_w_mfma_mb, dim3(18 * G), dim3(FBLK),
+                         0, s, r2, a1, bs, K, slab);
+    }
+    int perk_fold = (18432 + FBLK - 1) / FBLK;
+    hipLaunchKernelGGL(k_conv2_bwd_w_fold_mb, dim3(K * perk_fold),
+                       dim3(FBLK), 0, s, slab, grads_stack, P, o.w2, bs, K);
+    hipLaunchKernelGGL(k_conv2_bwd_b_mb, dim3(K * 64), dim3(FBLK), 0, s,
+                       dz2, grads_stack, P, o.b2, bs, K);
+    if (use_bf16)
+      hipLaunchKernelGGL(k_conv2_bwd_x_mfma_mb_bf16, dim3(G * 22), dim3(FBLK),
+                         0, s, dz2,
+                         reinterpret_cast<const __bf16*>(w2rot_stack),
+                         bs, K, a1, dz1);
+    else
+      hipLaunchKernelGGL(k_conv2_bwd_x_mfma_mb, dim3(G * 22), dim3(FBLK),
+                         0, s, dz2, w2rot_stack, a1, bs, K, dz1);
+    hipLaunchKernelGGL(k_conv1_bwd_w_mb, dim3(K * 32), dim3(1024), 0, s,
+                       xb, dz1, grads_stack, P, o.w1, o.b1, bs, K);
+    hipMemsetAsync(acc2k, 0, 2 * K * sizeof(double), s);
+    int blocks_per_k = (int)((P + SUMSQ_CHUNK - 1) / SUMSQ_CHUNK);
+    hipLaunchKernelGGL(k_sumsq_mb, dim3(K * blocks_per_k), dim3(FBLK), 0, s,
+                       grads_stack, P, blocks_per_k, acc2k);
+    hipLaunchKernelGGL(k_stats_mb, dim3((K + 63) / 64), dim3(64), 0, s,
+                       acc2k, K, max_norm, 1e-6f, stats_out);
+    hipLaunchKernelGGL(k_clip_sgd_mb, dim3(gkp), dim3(FBLK), 0, s,
+                       params_stack, grads_stack, P, K, acc2k, max_norm,
+                       1e-6f, lr_t, stats_out);
+  }
+  hipLaunchKernelGGL(k_pseudo_grad_mb, dim3(gkp), dim3(FBLK), 0, s,
+                     grads_stack, server_params, params_stack, weights_dev,
+                     P, K);
+  hipLaunchKernelGGL(k_accum_mb, dim3(gp), dim3(FBLK), 0, s,
+                     round_accum, grads_stack, P, K);
+}
+
+
+// ---------------------------------------------------------------------------
+// standalone entries for K-stacked flat arenas (reused by the
+// Shakespeare mega round's graph-captured epoch): per-client clip +
+// stats + SGD, and weighted pseudo-grad + deterministic accumulate.
+// ---------------------------------------------------------------------------
+extern "C" void launch_mega_clip_sgd(float* params_stack, float* grads_stack,
+                                     long long P, int K, double* acc2k,
+                                     float max_norm, const float* lr_t,
+                                     float* stats_out, hipStream_t s) {
+  hipMemsetAsync(acc2k, 0, 2 * K * sizeof(double), s);
+  int blocks_per_k = (int)((P + SUMSQ_CHUNK - 1) / SUMSQ_CHUNK);
+  hipLaunchKernelGGL(k_sumsq_mb, dim3(K * blocks_per_k), dim3(FBLK), 0, s,
+                     grads_stack, P, blocks_per_k, acc2k);
+  hipLaunchKernelGGL(k_stats_mb, dim3((K + 63) / 64), dim3(64), 0, s,
+                     acc2k, K, max_norm, 1e-6f, stats_out);
+  long long kp = (long long)K * P;
+  int gkp = (int)((kp + FBLK - 1) / FBLK); if (gkp > 4096) gkp = 4096;
+  hipLaunchKernelGGL(k_clip_sgd_mb, dim3(gkp), dim3(FBLK), 0, s,
+                     params_stack, grads_stack, P, K, acc2k, max_norm,
+                     1e-6f, lr_t, stats_out);
+}
+
+extern "C" void launch_mega_pseudo_accum(float* grads_stack,
+                                         const float* server,
+                                         const float* params_stack,
+                                         const float* weights_dev,
+                                         float* round_accum, long long P,
+                                         int K, hipStream_t s) {
+  long long kp = (long long)K * P;
+  int gkp = (int)((kp + FBLK - 1) / FBLK); if (gkp > 4096) gkp = 4096;
+  int gp = (int)((P + FBLK - 1) / FBLK); if (gp > 2048) gp = 2048;
+  hipLaunchKernelGGL(k_pseudo_grad_mb, dim3(gkp), dim3(FBLK), 0, s,
+                     grads_stack, server, params_stack, weights_dev, P, K);
+  hipLaunchKernelGGL(k_accum_mb, dim3(gp), dim3(FBLK), 0, s,
+                     round_accum, grads_stack, P, K);
+}
+
+// ---------------------------------------------------------------------------
+// debug/test launchers for the MFMA kernels (numerics tests call these
+// one-by-one against torch references — tests/test_mfma_gpu.py,
+// tests/test_bf16_gpu.py).  An operand that arrives as its own K-stack
+// is passed as the parameter stack with its own length as the stride P
+// and offset 0.
+// ---------------------------------------------------------------------------
+#define W2N 18432LL
+#define W3N 1179648LL
+
 extern "C" {
-void launch_w2_layouts(const float* w2, float* w2t, float* w2rot,
+void launch_w2_layouts(const float* w2, int K, float* w2t, float* w2rot,
                        hipStream_t s) {
-  hipLaunchKernelGGL(k_w2_layouts, dim3((18432 + FBLK - 1) / FBLK),
-                     dim3(FBLK), 0, s, w2, w2t, w2rot);
+  hipLaunchKernelGGL(k_w2_layouts_mb, dim3((K * 18432 + FBLK - 1) / FBLK),
+                     dim3(FBLK), 0, s, w2, W2N, 0LL, K, w2t, w2rot);
 }
 void launch_conv2_fwd_mfma(const float* a1, const float* w2t, const float* b2,
-                           int B, float* r2, hipStream_t s) {
-  hipLaunchKernelGGL(k_conv2_fwd_mfma, dim3(B * 9), dim3(FBLK), 0, s,
-                     a1, w2t, b2, B, r2);
+                           int bs, int K, float* r2, hipStream_t s) {
+  hipLaunchKernelGGL(k_conv2_fwd_mfma_mb, dim3(K * bs * 9), dim3(FBLK), 0, s,
+                     a1, w2t, b2, 64LL, 0LL, bs, K, r2);
 }
 void launch_conv2_bwd_x_mfma(const float* dz2, const float* w2rot,
-                             const float* a1, int B, float* dz1,
+                             const float* a1, int bs, int K, float* dz1,
                              hipStream_t s) {
-  hipLaunchKernelGGL(k_conv2_bwd_x_mfma, dim3(B * 11), dim3(FBLK), 0, s,
-                     dz2, w2rot, a1, B, dz1);
+  hipLaunchKernelGGL(k_conv2_bwd_x_mfma_mb, dim3(K * bs * 22), dim3(FBLK), 0,
+                     s, dz2, w2rot, a1, bs, K, dz1);
 }
-void launch_conv2_bwd_w_mfma(const float* dz2, const float* a1, int B,
+static void conv2_bwd_w_tail(const float* dz2, const float* slab, int bs,
+                             int K, float* dw2, float* db2, hipStream_t s) {
+  hipLaunchKernelGGL(k_conv2_bwd_w_fold_mb,
+                     dim3(K * ((18432 + FBLK - 1) / FBLK)), dim3(FBLK), 0, s,
+                     slab, dw2, W2N, 0LL, bs, K);
+  hipLaunchKernelGGL(k_conv2_bwd_b_mb, dim3(K * 64), dim3(FBLK), 0, s,
+                     dz2, db2, 64LL, 0LL, bs, K);
+}
+void launch_conv2_bwd_w_mfma(const float* dz2, const float* a1, int bs, int K,
                              float* dz2t, float* slab, float* dw2, float* db2,
                              hipStream_t s) {
-  hipLaunchKernelGGL(k_dz2_transpose, dim3((B * 36864 + FBLK - 1) / FBLK),
-                     dim3(FBLK), 0, s, dz2, B, dz2t);
-  hipLaunchKernelGGL(k_conv2_bwd_w_mfma, dim3(6 * B), dim3(FBLK), 0, s,
-                     dz2t, a1, B, slab);
-  hipLaunchKernelGGL(k_conv2_bwd_w_fold, dim3((18432 + FBLK - 1) / FBLK),
-                     dim3(FBLK), 0, s, slab, B, dw2);
-  hipLaunchKernelGGL(k_conv2_bwd_b, dim3(64), dim3(FBLK), 0, s, dz2, B, db2);
+  hipLaunchKernelGGL(k_dz2_transpose_mb,
+                     dim3((K * bs * 36864 + FBLK - 1) / FBLK), dim3(FBLK), 0,
+                     s, dz2, bs, K, dz2t);
+  hipLaunchKernelGGL(k_conv2_bwd_w_mfma_mb, dim3(18 * K * bs), dim3(FBLK), 0,
+                     s, dz2t, a1, bs, K, slab);
+  conv2_bwd_w_tail(dz2, slab, bs, K, dw2, db2, s);
 }
+// the seed arrives by value, so the fold runs the per-client wrapper once
+// per client (every client draws from the same seed)
 void launch_fc1_fwd_mfma(const float* a2, const float* w3, const float* b3,
-                         int B, float p2, unsigned long long seed,
+                         int bs, int K, float p2, unsigned long long seed,
                          unsigned long long offset, float* slab, float* z3,
                          float* a3, unsigned char* m3, hipStream_t s) {
-  hipLaunchKernelGGL(k_fc1_fwd_mfma, dim3(FC1_SPLIT), dim3(FBLK), 0, s,
-                     a2, w3, B, slab);
-  hipLaunchKernelGGL(k_fc1_fwd_reduce, dim3((B * 128 + FBLK - 1) / FBLK),
-                     dim3(FBLK), 0, s, slab, b3, B, p2, seed, offset,
-                     z3, a3, m3);
+  hipLaunchKernelGGL(k_fc1_fwd_mfma_mb, dim3(K * FC1_SPLIT), dim3(FBLK), 0, s,
+                     a2, w3, W3N, 0LL, bs, K, slab);
+  for (int k = 0; k < K; ++k)
+    hipLaunchKernelGGL(k_fc1_fwd_reduce, dim3((bs * 128 + FBLK - 1) / FBLK),
+                       dim3(FBLK), 0, s,
+                       slab + (long long)k * FC1_SPLIT * bs * 128,
+                       b3 + k * 128, bs, p2, seed, offset,
+                       z3 + k * bs * 128, a3 + k * bs * 128,
+                       m3 + k * bs * 128);
 }
-void launch_fc1_bwd_w_mfma(const float* dz3, const float* a2, int B,
+void launch_fc1_bwd_w_mfma(const float* dz3, const float* a2, int bs, int K,
                            float* dw3, float* db3, hipStream_t s) {
-  hipLaunchKernelGGL(k_fc1_bwd_w_mfma, dim3(144), dim3(FBLK), 0, s,
-                     dz3, a2, B, dw3);
-  hipLaunchKernelGGL(k_fc1_bwd_b, dim3(1), dim3(128), 0, s, dz3, B, db3);
+  hipLaunchKernelGGL(k_fc1_bwd_w_mfma_mb, dim3(K * 144), dim3(FBLK), 0, s,
+                     dz3, a2, dw3, W3N, 0LL, bs, K);
+  hipLaunchKernelGGL(k_fc1_bwd_b_mb, dim3(K), dim3(128), 0, s,
+                     dz3, db3, 128LL, 0LL, bs, K);
 }
-void launch_fc1_bwd_x_mfma(const float* dz3, const float* w3, int B,
+void launch_fc1_bwd_x_mfma(const float* dz3, const float* w3, int bs, int K,
                            float* da2, hipStream_t s) {
-  hipLaunchKernelGGL(k_fc1_bwd_x_mfma, dim3(144), dim3(FBLK), 0, s,
-                     dz3, w3, B, da2);
+  hipLaunchKernelGGL(k_fc1_bwd_x_mfma_mb, dim3(K * 144), dim3(FBLK), 0, s,
+                     dz3, w3, W3N, 0LL, bs, K, da2);
 }
+void launch_mfma_bf16_probe(const void* A, const void* B, float* D,
+                            hipStream_t s) {
+  hipLaunchKernelGGL(k_mfma_bf16_probe, dim3(1), dim3(64), 0, s,
+                     (const __bf16*)A, (const __bf16*)B, D);
 }
+void launch_fc1_fwd_mfma_bf16(const float* a2, const float* w3,
+                              const float* b3, int bs, int K, float p2,
+                              unsigned long long seed,
+                              unsigned long long offset, float* slab,
+                              float* z3, float* a3, unsigned char* m3,
+                              hipStream_t s) {
+  hipLaunchKernelGGL(k_fc1_fwd_mfma_mb_bf16, dim3(K * FC1B_SPLIT), dim3(FBLK),
+                     0, s, a2, w3, W3N, 0LL, bs, K, slab);
+  for (int k = 0; k < K; ++k)
+    hipLaunchKernelGGL(k_fc1_fwd_reduce_bf16,
+                       dim3((bs * 128 + FBLK - 1) / FBLK), dim3(FBLK), 0, s,
+                       slab + (long long)k * FC1B_SPLIT * bs * 128,
+                       b3 + k * 128, bs, p2, seed, offset,
+                       z3 + k * bs * 128, a3 + k * bs * 128,
+                       m3 + k * bs * 128);
+}
+// this kernel reads w2 and b2 through ONE stack pointer: w2b2 is K blocks
+// of [w2 (18432) | b2 (64)]
+void launch_conv2_fwd_mfma_bf16(const float* a1, const float* w2b2, int bs,
+                                int K, float* r2, hipStream_t s) {
+  hipLaunchKernelGGL(k_conv2_fwd_mfma_mb_bf16, dim3(K * bs * 9), dim3(FBLK),
+                     0, s, a1, w2b2, W2N + 64, 0LL, W2N, bs, K, r2);
+}
+void launch_conv2_bwd_x_mfma_bf16(const float* dz2, const float* w2,
+                                  const float* a1, int bs, int K,
+                                  float* w2rotbf, float* dz1, hipStream_t s) {
+  hipLaunchKernelGGL(k_w2rotbf_mb, dim3((K * 18432 + FBLK - 1) / FBLK),
+                     dim3(FBLK), 0, s, w2, W2N, 0LL, K,
+                     reinterpret_cast<__bf16*>(w2rotbf));
+  hipLaunchKernelGGL(k_conv2_bwd_x_mfma_mb_bf16, dim3(K * bs * 22),
+                     dim3(FBLK), 0, s, dz2,
+                     reinterpret_cast<const __bf16*>(w2rotbf), bs, K, a1,
+                     dz1);
+}
+void launch_conv2_bwd_w_mfma_bf16(const float* dz2, const float* a1, int bs,
+                                  int K, float* slab, float* dw2, float* db2,
+                                  hipStream_t s) {
+  hipLaunchKernelGGL(k_conv2_bwd_w_mfma_mb_bf16, dim3(18 * K * bs),
+                     dim3(FBLK), 0, s, dz2, a1, bs, K, slab);
+  conv2_bwd_w_tail(dz2, slab, bs, K, dw2, db2, s);
+}
+}  // extern "C"

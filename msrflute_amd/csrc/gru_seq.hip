@@ -13,6 +13,8 @@
 
 #include <hip/hip_runtime.h>
 
+#include "launchers.h"
+
 #define GRU_H 512
 
 __device__ inline float gsig(float x) { return 1.f / (1.f + __expf(-x)); }

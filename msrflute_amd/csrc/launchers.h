@@ -1,0 +1,189 @@
+// Host-side declarations shared by bindings.cpp and every .hip file that
+// defines or calls a launcher: the CNN workspace struct, the flat-arena
+// offsets of the CNN and the prototype of every extern "C" launcher.
+// Each definition includes this header, so a signature that disagrees
+// with its declaration fails to compile instead of corrupting a call.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+// arena offsets (fp32 indices) of the CNN-FEMNIST parameters for C classes
+struct CnnOffsets {
+  long long w1, b1, w2, b2, w3, b3, w4, b4, total;
+};
+
+inline CnnOffsets cnn_offsets(int C) {
+  CnnOffsets o;
+  o.w1 = 0;               // [32,1,3,3]
+  o.b1 = o.w1 + 288;      // [32]
+  o.w2 = o.b1 + 32;       // [64,32,3,3]
+  o.b2 = o.w2 + 18432;    // [64]
+  o.w3 = o.b2 + 64;       // [128,9216]
+  o.b3 = o.w3 + 1179648;  // [128]
+  o.w4 = o.b3 + 128;      // [C,128]
+  o.b4 = o.w4 + (long long)C * 128;  // [C]
+  o.total = o.b4 + C;
+  return o;
+}
+
+// per-client CNN workspace, laid out inside one float buffer by the
+// binding (sizes for B rows)
+struct CnnWorkspace {
+  float *xb, *a1, *r2, *a2, *z3, *a3, *dlogits, *dz3, *da2, *dz2, *dz1;
+  float *wsl;  // split-K partial slab (B*18432 floats), shared fwd/bwd
+  float *w2t, *w2rot;  // per-batch W2 fragment layouts (18432 floats each)
+  int *yb;
+  unsigned char *pidx, *m2, *m3;
+  double *red_partials, *red_acc;
+};
+
+extern "C" {
+
+// flat_ops.hip
+void launch_pseudo_grad(float* out, const float* ws, const float* wt,
+                        float weight, long long n, hipStream_t s);
+void launch_axpy(float* y, const float* x, float alpha, long long n,
+                 hipStream_t s);
+void launch_scale(float* x, float alpha, long long n, hipStream_t s);
+void launch_sum_sumsq(const float* x, long long n, double* out2,
+                      hipStream_t s);
+void launch_sum_sumsq2(const float* x, long long n, double* partials,
+                       double* out2, hipStream_t s);
+int sum_sumsq2_partials(long long n);
+void launch_clip_apply(float* x, long long n, const double* out2,
+                       float max_norm, float eps, float* norm_out,
+                       hipStream_t s);
+void launch_add_gaussian_noise(float* x, long long n, float sigma,
+                               unsigned long long seed,
+                               unsigned long long offset, hipStream_t s);
+void launch_sgd_step(float* p, const float* g, float* buf, float lr,
+                     const float* lr_ptr, float momentum, float dampening,
+                     float weight_decay, int nesterov, int first_step,
+                     long long n, hipStream_t s);
+void launch_clip_apply_stats(float* x, long long n, const double* out2,
+                             float max_norm, float eps, float* stats_acc,
+                             hipStream_t s);
+void launch_adam_step(float* p, const float* g, float* m, float* v,
+                      float* vmax, float lr, float beta1, float beta2,
+                      float eps, float weight_decay, float bc1, float bc2,
+                      int amsgrad, int adamw, long long n, hipStream_t s);
+void launch_adamax_step(float* p, const float* g, float* m, float* u,
+                        float lr, float beta1, float beta2, float eps,
+                        float weight_decay, float bc1, long long n,
+                        hipStream_t s);
+void launch_segmented_sqnorm(const float* x, const long long* offs,
+                             int n_segs, double* out, hipStream_t s);
+void launch_quant_bin_mask(float* x, long long n, const float* min_t,
+                           const float* max_t, const float* thresh_t,
+                           int n_bins, hipStream_t s);
+void launch_gru_gates(const float* g_i, const float* g_h, const float* h,
+                      float* out, int B, int H, hipStream_t s);
+
+// lstm_seq.hip
+void launch_lstm_seq_fwd(const float* xp, const float* w_hh_t, float* h_seq,
+                         float* gates, float* c_seq, int B, int T, int H,
+                         hipStream_t s);
+void launch_lstm_seq_bwd(const float* gates, const float* c_seq,
+                         const float* w_hh, const float* dh_out,
+                         float* dg_pre, int B, int T, int H, hipStream_t s);
+void launch_lstm_seq_fwd_b(const float* xp, const float* w_hh_t_stack,
+                           float* h_seq, float* gates, float* c_seq, int R,
+                           int rows_per_client, int T, hipStream_t s);
+void launch_lstm_seq_bwd_b(const float* gates, const float* c_seq,
+                           const float* w_hh_stack, const float* dh_out,
+                           float* dg_pre, int R, int rows_per_client, int T,
+                           hipStream_t s);
+
+// gru_seq.hip
+void launch_gru_seq_fwd(const float* gi, const float* whh_t,
+                        const float* b_hh, float* h_seq, float* gates,
+                        float* ghn, int B, int T, hipStream_t s);
+void launch_gru_seq_bwd(const float* gates, const float* ghn,
+                        const float* h_seq, const float* w_hh,
+                        const float* dh_out, float* dgi, float* dgh,
+                        int B, int T, hipStream_t s);
+
+// fused_cnn.hip — drivers
+void launch_cnn_epoch(
+    const float* shard_x, const long long* shard_y, const long long* order,
+    long long n, int bs, int C, float* params, float* grads,
+    CnnWorkspace ws, const float* lr_t, float max_norm, float p1, float p2,
+    float* stats_acc, float* loss_acc, unsigned long long seed,
+    hipStream_t s, long long row_base, int use_bf16);
+void launch_cnn_round(
+    const float* shard_x, const long long* shard_y,
+    const long long* orders,            // concatenated per-client shuffles
+    const long long* row_bases,         // HOST: K shard row offsets
+    const long long* order_offs,        // HOST: K offsets into `orders`
+    const long long* counts,            // HOST: K sample counts
+    const float* weights,               // HOST: K aggregation weights
+    const unsigned long long* seeds,    // HOST: K dropout seeds
+    int K, int bs, int C,
+    const float* server_params, float* params, float* grads,
+    float* round_accum, CnnWorkspace ws, const float* lr_t, float max_norm,
+    float p1, float p2, float* stats_out, float* loss_out,
+    hipStream_t s, int use_bf16);
+void launch_cnn_round_mega(
+    const float* shard_x, const long long* shard_y,
+    const long long* orders_dev,
+    const long long* row_bases_dev, const long long* order_offs_dev,
+    const long long* counts_dev, const long long* counts_host,
+    const float* weights_dev, const long long* seeds_dev,
+    int K, int bs, int C,
+    const float* server_params, float* params_stack, float* grads_stack,
+    float* round_accum,
+    float* xb, float* a1, float* r2, float* a2, float* z3, float* a3,
+    float* dlogits, float* dz3, float* da2, float* dz2, float* dz1,
+    float* w2t_stack, float* w2rot_stack, float* slab,
+    int* yb, unsigned char* pidx, unsigned char* m2, unsigned char* m3,
+    double* acc2k,
+    const float* lr_t, float max_norm, float p1, float p2,
+    float* stats_out, float* loss_out, hipStream_t s, int use_bf16);
+void launch_mega_clip_sgd(float* params_stack, float* grads_stack,
+                          long long P, int K, double* acc2k, float max_norm,
+                          const float* lr_t, float* stats_out, hipStream_t s);
+void launch_mega_pseudo_accum(float* grads_stack, const float* server,
+                              const float* params_stack,
+                              const float* weights_dev, float* round_accum,
+                              long long P, int K, hipStream_t s);
+
+// fused_cnn.hip — per-kernel debug launchers.  Every operand is a
+// K-stack (client k's rows are [k*bs, (k+1)*bs), its weights / biases /
+// gradients the k-th contiguous block); K = 1 is the per-client case.
+void launch_w2_layouts(const float* w2, int K, float* w2t, float* w2rot,
+                       hipStream_t s);
+void launch_conv2_fwd_mfma(const float* a1, const float* w2t,
+                           const float* b2, int bs, int K, float* r2,
+                           hipStream_t s);
+void launch_conv2_bwd_x_mfma(const float* dz2, const float* w2rot,
+                             const float* a1, int bs, int K, float* dz1,
+                             hipStream_t s);
+void launch_conv2_bwd_w_mfma(const float* dz2, const float* a1, int bs,
+                             int K, float* dz2t, float* slab, float* dw2,
+                             float* db2, hipStream_t s);
+void launch_fc1_fwd_mfma(const float* a2, const float* w3, const float* b3,
+                         int bs, int K, float p2, unsigned long long seed,
+                         unsigned long long offset, float* slab, float* z3,
+                         float* a3, unsigned char* m3, hipStream_t s);
+void launch_fc1_bwd_w_mfma(const float* dz3, const float* a2, int bs, int K,
+                           float* dw3, float* db3, hipStream_t s);
+void launch_fc1_bwd_x_mfma(const float* dz3, const float* w3, int bs, int K,
+                           float* da2, hipStream_t s);
+void launch_mfma_bf16_probe(const void* A, const void* B, float* D,
+                            hipStream_t s);
+void launch_fc1_fwd_mfma_bf16(const float* a2, const float* w3,
+                              const float* b3, int bs, int K, float p2,
+                              unsigned long long seed,
+                              unsigned long long offset, float* slab,
+                              float* z3, float* a3, unsigned char* m3,
+                              hipStream_t s);
+void launch_conv2_fwd_mfma_bf16(const float* a1, const float* w2b2, int bs,
+                                int K, float* r2, hipStream_t s);
+void launch_conv2_bwd_x_mfma_bf16(const float* dz2, const float* w2,
+                                  const float* a1, int bs, int K,
+                                  float* w2rotbf, float* dz1, hipStream_t s);
+void launch_conv2_bwd_w_mfma_bf16(const float* dz2, const float* a1, int bs,
+                                  int K, float* slab, float* dw2, float* db2,
+                                  hipStream_t s);
+
+}  // extern "C"

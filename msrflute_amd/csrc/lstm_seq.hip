@@ -22,6 +22,8 @@
 
 #include <hip/hip_runtime.h>
 
+#include "launchers.h"
+
 #define LSTM_H 256           // hidden size of the benchmark model
 
 __device__ inline float sigf(float x) { return 1.f / (1.f + __expf(-x)); }

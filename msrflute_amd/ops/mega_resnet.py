@@ -17,7 +17,7 @@ the 256-CU chip.  Here all K sampled clients train together:
   cross-batch stat pollution and no running buffers;
 * per-client clip + sufficient stats + SGD and the weighted pseudo-grad
   accumulate reuse the generic K-stacked kernels (_C.mega_clip_sgd /
-  _C.mega_pseudo_accum, csrc/fused_cnn_mega.hip);
+  _C.mega_pseudo_accum, csrc/fused_cnn.hip);
 * the WHOLE local epoch is captured as one hipGraph, captured on the
   first round's REAL gather indices (capture-safety lesson from the
   Shakespeare round: degenerate capture data can bake value-dependent

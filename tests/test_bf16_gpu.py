@@ -36,30 +36,52 @@ def _bf16_ref_conv2(a1, w2, b2=None):
     return out
 
 
-def test_conv2_fwd_mfma_bf16():
-    B = 13
+def _per_client(fn, K, *stacked):
+    """cat of fn(k-th block of every stacked tensor) over the K clients"""
+    return torch.cat([fn(*(t[k] for t in stacked)) for k in range(K)])
+
+
+def _stacked(rows_k1):
+    """(K clients, rows per client): the K=1 shape each test always used,
+    and two clients of 3 rows with independent weights, referenced client
+    by client (a wrong client stride reads the other client's weights)."""
+    return pytest.mark.parametrize("K,bs", [(1, rows_k1), (2, 3)])
+
+
+@_stacked(13)
+def test_conv2_fwd_mfma_bf16(K, bs):
+    B = K * bs
     torch.manual_seed(1)
     a1 = _rand(B, 32, 26, 26).abs()
-    w2, b2 = _rand(64, 32, 3, 3), _rand(64)
-    ref = torch.nn.functional.relu(_bf16_ref_conv2(a1, w2, b2))
+    w2, b2 = _rand(K, 64, 32, 3, 3), _rand(K, 64)
+    ref = _per_client(
+        lambda a, w, b: torch.nn.functional.relu(_bf16_ref_conv2(a, w, b)),
+        K, a1.view(K, bs, 32, 26, 26), w2, b2)
     out = _C.dbg_conv2_fwd_mfma_bf16(a1.reshape(-1).contiguous(),
-                                     w2.reshape(-1).contiguous(), b2, B)
+                                     w2.reshape(-1).contiguous(),
+                                     b2.reshape(-1).contiguous(), B)
     out = out.view(B, 64, 24, 24)
     # same bf16-rounded inputs, different f32 accumulation order
     assert torch.allclose(out, ref, rtol=2e-2, atol=5e-2), \
         (out - ref).abs().max().item()
 
 
-def test_conv2_bwd_x_mfma_bf16():
-    B = 7
+@_stacked(7)
+def test_conv2_bwd_x_mfma_bf16(K, bs):
+    B = K * bs
     torch.manual_seed(2)
     a1 = _rand(B, 32, 26, 26)
-    w2 = _rand(64, 32, 3, 3)
+    w2 = _rand(K, 64, 32, 3, 3)
     dz2 = _rand(B, 64, 24, 24)
-    x = a1.clamp(min=0).detach().to(torch.bfloat16).float().requires_grad_(True)
-    y = torch.nn.functional.conv2d(x, w2.to(torch.bfloat16).float())
-    y.backward(dz2.to(torch.bfloat16).float())
-    ref = x.grad * (a1 > 0)
+
+    def ref_client(a, w, dz):
+        x = a.clamp(min=0).detach().to(torch.bfloat16).float() \
+            .requires_grad_(True)
+        y = torch.nn.functional.conv2d(x, w.to(torch.bfloat16).float())
+        y.backward(dz.to(torch.bfloat16).float())
+        return x.grad * (a > 0)
+    ref = _per_client(ref_client, K, a1.view(K, bs, 32, 26, 26), w2,
+                      dz2.view(K, bs, 64, 24, 24))
     out = _C.dbg_conv2_bwd_x_mfma_bf16(dz2.reshape(-1).contiguous(),
                                        w2.reshape(-1).contiguous(),
                                        a1.reshape(-1).contiguous(), B)
@@ -68,34 +90,44 @@ def test_conv2_bwd_x_mfma_bf16():
         (out - ref).abs().max().item()
 
 
-def test_conv2_bwd_w_mfma_bf16():
-    B = 20
+@_stacked(20)
+def test_conv2_bwd_w_mfma_bf16(K, bs):
+    B = K * bs
     torch.manual_seed(3)
     a1 = _rand(B, 32, 26, 26).abs()
     dz2 = _rand(B, 64, 24, 24)
-    w = torch.zeros(64, 32, 3, 3, device="cuda", requires_grad=True)
-    y = torch.nn.functional.conv2d(a1.to(torch.bfloat16).float(), w)
-    y.backward(dz2.to(torch.bfloat16).float())
-    ref_w = w.grad
+
+    def ref_client(a, dz):
+        w = torch.zeros(64, 32, 3, 3, device="cuda", requires_grad=True)
+        y = torch.nn.functional.conv2d(a.to(torch.bfloat16).float(), w)
+        y.backward(dz.to(torch.bfloat16).float())
+        return w.grad
+    a1k, dz2k = a1.view(K, bs, 32, 26, 26), dz2.view(K, bs, 64, 24, 24)
+    ref_w = _per_client(ref_client, K, a1k, dz2k)
     dw2, db2 = _C.dbg_conv2_bwd_w_mfma_bf16(dz2.reshape(-1).contiguous(),
-                                            a1.reshape(-1).contiguous(), B)
-    # K = 11520 bf16 products in f32 accum: scale tolerance to magnitude
+                                            a1.reshape(-1).contiguous(), B, K)
+    # bs * 576 bf16 products in f32 accum: scale tolerance to magnitude
     scale = ref_w.abs().max()
-    assert torch.allclose(dw2.view(64, 32, 3, 3), ref_w,
+    assert torch.allclose(dw2.view(K * 64, 32, 3, 3), ref_w,
                           rtol=2e-2, atol=2e-2 * float(scale)), \
-        (dw2.view(64, 32, 3, 3) - ref_w).abs().max().item()
-    assert torch.allclose(db2, dz2.sum(dim=(0, 2, 3)), rtol=1e-3, atol=1e-2)
+        (dw2.view(K * 64, 32, 3, 3) - ref_w).abs().max().item()
+    assert torch.allclose(db2, dz2k.sum(dim=(1, 3, 4)).reshape(-1),
+                          rtol=1e-3, atol=1e-2)
 
 
-def test_fc1_fwd_mfma_bf16():
-    B = 20
+@_stacked(20)
+def test_fc1_fwd_mfma_bf16(K, bs):
+    B = K * bs
     torch.manual_seed(4)
     a2 = _rand(B, 9216)
-    w3, b3 = _rand(128, 9216) * 0.02, _rand(128)
-    ref_z = (a2.to(torch.bfloat16).float()
-             @ w3.to(torch.bfloat16).float().t() + b3)
+    w3, b3 = _rand(K, 128, 9216) * 0.02, _rand(K, 128)
+    ref_z = _per_client(
+        lambda a, w, b: (a.to(torch.bfloat16).float()
+                         @ w.to(torch.bfloat16).float().t() + b),
+        K, a2.view(K, bs, 9216), w3, b3)
     z3, a3, m3 = _C.dbg_fc1_fwd_mfma_bf16(a2.reshape(-1).contiguous(),
-                                          w3.reshape(-1).contiguous(), b3,
+                                          w3.reshape(-1).contiguous(),
+                                          b3.reshape(-1).contiguous(),
                                           B, 0.0, 123, 0)
     assert torch.allclose(z3.view(B, 128), ref_z, rtol=2e-2, atol=5e-2), \
         (z3.view(B, 128) - ref_z).abs().max().item()

@@ -1,4 +1,4 @@
-"""Cross-client MEGA round (csrc/fused_cnn_mega.hip): one launch set per
+"""Cross-client MEGA round (csrc/fused_cnn.hip): one launch set per
 batch-step for all K clients must match the per-executor fused round
 (same per-client kernels + Philox dropout streams; only the clip-norm
 partial-sum order and float accumulation order differ)."""
