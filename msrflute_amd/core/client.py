@@ -18,6 +18,7 @@ from __future__ import annotations
 import logging
 import os
 import time
+from itertools import accumulate
 from typing import Dict, Optional
 
 import torch
@@ -26,6 +27,7 @@ from .. import ops
 from ..models import make_model
 from ..ops.arena import ParameterArena
 from ..ops.fused_optim import make_arena_optimizer
+from ..ops.mega_round import lookup_round, plan_round, round_outputs
 from ..strategies import select_strategy
 from ..utils import (ScheduledSamplingScheduler, alpha_update, make_optimizer,
                      print_rank, to_device)
@@ -524,6 +526,11 @@ class ClientPool:
         self.round_accums = [server_arena.new_buffer() for _ in self.executors]
         self._rr = 0
         self._streams_dirty = False
+        # whole-round drivers, built on first use: None = not probed yet,
+        # False = not this model (stop probing), else the driver
+        self._mega = None          # ops.fused_cnn.MegaRound
+        self._mega_lstm = None     # ops.mega_shakespeare.ShakespeareMegaRound
+        self._mega_resnet = None   # ops.mega_resnet.ResNetMegaRound
 
     # properties the server reads off the executor
     @property
@@ -572,6 +579,153 @@ class ClientPool:
             acc.zero_()
         self._streams_dirty = False
 
+    # ------------------------------------------------------------------
+    def run_fused_round_batch(self, client_ids, initial_lr, iteration,
+                              seeds):
+        """Train the round's clients with a whole-round driver, tried in
+        order: Shakespeare mega round, ResNet mega round, CNN mega round,
+        one _C.cnn_round per executor (on its stream) covering its chunk
+        of the clients.  Returns outputs or None if no driver is eligible
+        (caller falls back to the per-client path).  Eligibility is
+        validated UP FRONT so no partial state is mutated on the
+        fallback path."""
+        prim = self.executors[0]
+        cc = prim.client_config
+        data_cfg = cc["data_config"]["train"]
+        if not _fused_round_eligible(prim, data_cfg):
+            return None
+        out = self._try_graphed_mega("_mega_lstm", True, _build_mega_lstm,
+                                     data_cfg, client_ids, initial_lr, seeds)
+        if out is None:
+            # OPT-IN: measured SLOWER than the per-client epoch-graph path
+            # on ROCm 7.2 — MIOpen decomposes groups=K convs into K
+            # per-group kernels (no batching win) and grouped bwd-weight
+            # falls to multi-ms CK batched-GEMM fallbacks (PERF.md,
+            # profiles/).  The formulation itself is exact
+            # (tests/test_mega_cpu.py, f64) and flips on wholesale when a
+            # ROCm release makes grouped conv competitive.
+            out = self._try_graphed_mega(
+                "_mega_resnet", cc.get("use_mega_round_resnet", False),
+                _build_mega_resnet, data_cfg, client_ids, initial_lr, seeds)
+        if out is not None:
+            return out
+        fc = prim.fused_cnn
+        if fc is None:
+            return None
+        store = prim._get_shard_store(data_cfg)
+        if store is None or store.x[0].numel() != 784:
+            return None
+        ds = train_dataset
+        if ds is None:
+            return None
+        dms = data_cfg.get("desired_max_samples", None)
+        if lookup_round(store, ds.user_list, client_ids, dms) is None:
+            return None
+
+        # cross-client MEGA round: one launch set per batch-step covering
+        # all K clients
+        if cc.get("use_mega_round", True):
+            if self._mega is None:
+                from ..ops.fused_cnn import MegaRound
+                self._mega = MegaRound(prim.arena, fc.C, fc.bs, fc.p1, fc.p2,
+                                       data_cfg.get("max_grad_norm"),
+                                       use_bf16=fc.use_bf16)
+            if self._mega.supports(len(client_ids)):
+                out = self._mega.run(store, ds, client_ids, seeds, initial_lr,
+                                     self.server_arena, self.round_accums[0],
+                                     dms)
+                if out is not None:
+                    self._mega_round_done(len(client_ids))
+                    return out
+
+        # per-executor fused rounds: each chunk's shuffle orders are drawn
+        # right before its launch, so the host work of chunk k+1 overlaps
+        # the GPU work of chunk k
+        for ex in self.executors[1:]:
+            if not ex._shard_store_tried:
+                ex._shard_store = store
+                ex._shard_store_tried = True
+        P = len(self.executors)
+        outputs = []
+        for k in range(P):
+            chunk, schunk = client_ids[k::P], seeds[k::P]
+            if not chunk:
+                continue
+            ex, st = self.executors[k], self.streams[k]
+            st.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(st):
+                plan = plan_round(store, ds.user_list, chunk, schunk, dms)
+                outputs.extend(_fused_round_impl(
+                    ex, store, plan, chunk, schunk, initial_lr,
+                    self.round_accums[k]))
+            self._streams_dirty = True
+        return outputs
+
+    def _try_graphed_mega(self, attr, enabled, build, data_cfg, client_ids,
+                          initial_lr, seeds):
+        """One graph-captured cross-client round
+        (ops/mega_round.GraphedMegaRound) when the model being trained is
+        the one ``build(prim, data_cfg)`` recognises (it returns the
+        driver, or None for any other model); the driver is kept in
+        ``self.<attr>``.  Returns outputs or None if not this task /
+        ineligible."""
+        prim = self.executors[0]
+        cc = prim.client_config
+        if getattr(self, attr) is False or not enabled:
+            return None
+        if not cc.get("use_mega_round", True) or cc.get("mixed_precision"):
+            return None  # the graphed rounds are fp32
+        if prim.arena is None or prim.arena.device.type != "cuda":
+            return None
+        opt_cfg = cc.get("optimizer_config", {})
+        if (opt_cfg.get("type", "sgd") != "sgd"
+                or opt_cfg.get("momentum", 0) or opt_cfg.get("weight_decay", 0)
+                or opt_cfg.get("nesterov", False)):
+            return None
+        if getattr(self, attr) is None:
+            mega = build(prim, data_cfg) if ops.HAS_EXT else None
+            setattr(self, attr, mega or False)
+        mega = getattr(self, attr)
+        if mega is False or not mega.supports(len(client_ids)):
+            return None
+        store = prim._get_shard_store(data_cfg)
+        if store is None or train_dataset is None:
+            return None
+        out = mega.run(store, train_dataset, client_ids, seeds, initial_lr,
+                       self.server_arena, self.round_accums[0],
+                       data_cfg.get("desired_max_samples", None))
+        if out is not None:
+            self._mega_round_done(len(client_ids))
+        return out
+
+    def _mega_round_done(self, n_clients):
+        """A cross-client round ran on the current stream into
+        ``round_accums[0]``."""
+        self._streams_dirty = True
+        prim = self.executors[0]
+        prim.perf_acc["clients"] = prim.perf_acc.get("clients", 0) + n_clients
+
+
+def _build_mega_lstm(prim, data_cfg):
+    """The Shakespeare char-LSTM mega round (ops/mega_shakespeare.py), or
+    None if ``prim`` trains another model."""
+    from ..ops.mega_shakespeare import ShakespeareMegaRound, matches_char_lstm
+    if matches_char_lstm(prim.arena) is None:
+        return None
+    return ShakespeareMegaRound(prim.arena, data_cfg.get("batch_size", 4),
+                                data_cfg.get("max_grad_norm"))
+
+
+def _build_mega_resnet(prim, data_cfg):
+    """The fed-CIFAR100 ResNet-18 mega round (ops/mega_resnet.py), or None
+    if ``prim`` trains another model (or one without GroupNorm)."""
+    from ..ops.mega_resnet import ResNetMegaRound, matches_resnet18
+    cpg = int(prim.model_config.get("group_norm", 0) or 0)
+    if cpg <= 0 or matches_resnet18(prim.arena) is None:
+        return None
+    return ResNetMegaRound(prim.arena, data_cfg.get("batch_size", 20),
+                           data_cfg.get("max_grad_norm"), cpg)
+
 
 def _fused_round_eligible(ex, data_cfg):
     """The fused whole-round driver trains full shards with plain SGD and
@@ -579,8 +733,8 @@ def _fused_round_eligible(ex, data_cfg):
     whenever the eager path would behave differently: a frozen layer
     (its pseudo-grad segment must be zeroed, fedavg.py:58) or a
     num_skips_threshold (clients can be zero-weighted mid-epoch).
-    desired_max_samples is checked per client against shard sizes by the
-    callers (the eager path truncates each client's epoch there)."""
+    desired_max_samples is checked per client against shard sizes by
+    lookup_round (the eager path truncates each client's epoch there)."""
     if ex.model_config.get("freeze_layer", None):
         return False
     if int(ex.client_config.get("num_skips_threshold", -1)) >= 0:
@@ -588,44 +742,16 @@ def _fused_round_eligible(ex, data_cfg):
     return True
 
 
-def _fused_round_impl(ex, client_ids, initial_lr, seeds):
-    """One _C.cnn_round call training all of ``ex``'s clients for this
-    round (copy-in, fused epoch, weighted pseudo-grad, accumulate into
-    ``ex.round_accum_target``).  Returns outputs or None if ineligible."""
-    if ex.fused_cnn is None:
-        return None
-    data_cfg = ex.client_config["data_config"]["train"]
-    if not _fused_round_eligible(ex, data_cfg):
-        return None
-    store = ex._get_shard_store(data_cfg)
-    if store is None or store.x[0].numel() != 784:
-        return None
-    import msrflute_amd.core.client as cm
-    ds = cm.train_dataset
-    if ds is None:
-        return None
+def _fused_round_impl(ex, store, plan, client_ids, seeds, initial_lr,
+                      round_accum):
+    """One _C.cnn_round call training ``client_ids`` on ``ex`` as planned
+    (plan_round): copy-in, fused epoch, weighted pseudo-grad, accumulate
+    into ``round_accum``.  Returns the per-client outputs."""
     fc = ex.fused_cnn
-    dms = data_cfg.get("desired_max_samples", None)
-    counts, row_bases, order_offs, orders, w_list = [], [], [], [], []
-    off = 0
-    for cid, seed in zip(client_ids, seeds):
-        user = ds.user_list[cid]
-        i = store.user_pos.get(user)
-        if i is None:
-            return None
-        lo, hi = store.offsets[i], store.offsets[i + 1]
-        n = hi - lo
-        if n == 0 or (dms is not None and n > dms):
-            return None
-        torch.manual_seed(seed & 0x7FFFFFFFFFFF)
-        orders.append(torch.randperm(n))
-        counts.append(n)
-        row_bases.append(lo)
-        order_offs.append(off)
-        off += n
-        w_list.append(float(n))  # FedAvg weight = num_samples
+    counts, row_bases, orders = plan
     K = len(client_ids)
-    orders_cat = torch.cat(orders) if orders else torch.empty(0, dtype=torch.int64)
+    off = sum(counts)
+    order_offs = [0] + list(accumulate(counts))[:-1]
     if getattr(ex, "_order_pin", None) is None or ex._order_pin.numel() < off:
         ex._order_pin = torch.empty(max(off, 1024),
                                     dtype=torch.int64).pin_memory()
@@ -635,7 +761,7 @@ def _fused_round_impl(ex, client_ids, initial_lr, seeds):
         # queued; overwriting the pinned staging before it lands would
         # corrupt that round's shuffle orders
         ex._order_pin_ev.synchronize()
-    ex._order_pin[:off].copy_(orders_cat)
+    ex._order_pin[:off].copy_(torch.cat(orders))
     orders_dev = ex._order_pin[:off].to(ex.arena.device, non_blocking=True)
     ex._order_pin_ev = torch.cuda.Event()
     ex._order_pin_ev.record()
@@ -646,237 +772,17 @@ def _fused_round_impl(ex, client_ids, initial_lr, seeds):
     ex._round_stats[: 2 * K].zero_()
     ex._round_loss[:K].zero_()
     fc.lr_t.fill_(float(initial_lr))
-    ops_mod = ops
-    _ = ops_mod  # (ops imported at module top)
-    from msrflute_amd import _C
-    _C.cnn_round(
+    ops._C.cnn_round(
         store.x.reshape(len(store.y), -1), store.y, orders_dev,
         torch.tensor(row_bases, dtype=torch.int64),
         torch.tensor(order_offs, dtype=torch.int64),
         torch.tensor(counts, dtype=torch.int64),
-        torch.tensor(w_list, dtype=torch.float32),
+        torch.tensor(counts, dtype=torch.float32),  # FedAvg: num_samples
         torch.tensor([s & 0x7FFFFFFFFFFF for s in seeds], dtype=torch.int64),
         fc.bs, fc.C, ex.server_arena.data, ex.arena.data, ex.arena.grad,
-        ex.round_accum_target, fc.work_f, fc.work_i, fc.work_b, fc.work_d,
+        round_accum, fc.work_f, fc.work_i, fc.work_b, fc.work_d,
         fc.lr_t, fc.max_norm, fc.p1, fc.p2,
         ex._round_stats, ex._round_loss, fc.use_bf16)
-    outputs = []
-    now = time.time()
-    for k, cid in enumerate(client_ids):
-        n_batches = (counts[k] + fc.bs - 1) // fc.bs
-        outputs.append((cid, {
-            "cs": {"setup": 0.0, "training": 0.0, "full cost": 0.0,
-                   "dataloader": 0.0},
-            "ns": counts[k],
-            "pl": {"weight": w_list[k], "grad": None, "pooled": True},
-            "_lazy": (ex._round_loss[k].reshape(()),
-                      ex._round_stats[2 * k: 2 * k + 2],
-                      n_batches * ex.arena.total),
-            "ts": now,
-        }))
-        ex.perf_acc["clients"] = ex.perf_acc.get("clients", 0) + 1
-    return outputs
-
-
-def _try_mega_lstm_round(self, prim, data_cfg, client_ids, initial_lr,
-                         seeds):
-    """Cross-client MEGA round for the Shakespeare char-LSTM
-    (ops/mega_shakespeare.py): all K clients' epochs in one graph-captured
-    launch set (batched recurrence kernels + bmm projections over
-    K-stacked weights).  Returns outputs or None if not this task /
-    ineligible."""
-    if self._mega_lstm is False:
-        return None
-    if not prim.client_config.get("use_mega_round", True):
-        return None
-    if prim.client_config.get("mixed_precision"):
-        return None  # the LSTM path is fp32
-    if prim.arena is None or prim.arena.device.type != "cuda":
-        return None
-    opt_cfg = prim.client_config.get("optimizer_config", {})
-    if (opt_cfg.get("type", "sgd") != "sgd"
-            or opt_cfg.get("momentum", 0) or opt_cfg.get("weight_decay", 0)
-            or opt_cfg.get("nesterov", False)):
-        return None
-    if self._mega_lstm is None:
-        from ..ops import HAS_EXT
-        from ..ops.mega_shakespeare import (ShakespeareMegaRound,
-                                            matches_char_lstm)
-        if not HAS_EXT or matches_char_lstm(prim.arena) is None:
-            self._mega_lstm = False  # not this model: stop probing
-            return None
-        self._mega_lstm = ShakespeareMegaRound(
-            prim.arena, data_cfg.get("batch_size", 4),
-            data_cfg.get("max_grad_norm"))
-    if not self._mega_lstm.supports(len(client_ids)):
-        return None
-    store = prim._get_shard_store(data_cfg)
-    if store is None or store.x.dim() != 2:
-        return None
-    import msrflute_amd.core.client as cm
-    ds = cm.train_dataset
-    if ds is None:
-        return None
-    dms = data_cfg.get("desired_max_samples", None)
-    for cid in client_ids:
-        i = store.user_pos.get(ds.user_list[cid])
-        if i is None:
-            return None
-        n = store.offsets[i + 1] - store.offsets[i]
-        if n == 0 or (dms is not None and n > dms):
-            return None
-    out = self._mega_lstm.run(store, ds, client_ids, seeds, initial_lr,
-                              self.server_arena, self.round_accums[0])
-    if out is not None:
-        self._streams_dirty = True
-        prim.perf_acc["clients"] = (prim.perf_acc.get("clients", 0)
-                                    + len(client_ids))
-    return out
-
-
-def _try_mega_resnet_round(self, prim, data_cfg, client_ids, initial_lr,
-                           seeds):
-    """Cross-client MEGA round for the fed-CIFAR100 ResNet-18
-    (ops/mega_resnet.py): all K clients' epochs as one graph-captured
-    launch set of grouped convs + GroupNorm over K-stacked weights.
-
-    OPT-IN (use_mega_round_resnet): measured SLOWER than the per-client
-    epoch-graph path on ROCm 7.2 — MIOpen decomposes groups=K convs into
-    K per-group kernels (no batching win) and grouped bwd-weight falls
-    to multi-ms CK batched-GEMM fallbacks (PERF.md, profiles/).  The
-    formulation itself is exact (tests/test_mega_cpu.py, f64) and flips
-    on wholesale when a ROCm release makes grouped conv competitive."""
-    if self._mega_resnet is False:
-        return None
-    if not prim.client_config.get("use_mega_round_resnet", False):
-        return None
-    if not prim.client_config.get("use_mega_round", True):
-        return None
-    if prim.client_config.get("mixed_precision"):
-        return None
-    if prim.arena is None or prim.arena.device.type != "cuda":
-        return None
-    opt_cfg = prim.client_config.get("optimizer_config", {})
-    if (opt_cfg.get("type", "sgd") != "sgd"
-            or opt_cfg.get("momentum", 0) or opt_cfg.get("weight_decay", 0)
-            or opt_cfg.get("nesterov", False)):
-        return None
-    if self._mega_resnet is None:
-        from ..ops import HAS_EXT
-        from ..ops.mega_resnet import ResNetMegaRound, matches_resnet18
-        cpg = int(prim.model_config.get("group_norm", 0) or 0)
-        if (not HAS_EXT or cpg <= 0
-                or matches_resnet18(prim.arena) is None):
-            self._mega_resnet = False  # not this model: stop probing
-            return None
-        self._mega_resnet = ResNetMegaRound(
-            prim.arena, data_cfg.get("batch_size", 20),
-            data_cfg.get("max_grad_norm"), cpg)
-    if not self._mega_resnet.supports(len(client_ids)):
-        return None
-    store = prim._get_shard_store(data_cfg)
-    if store is None or store.x.dim() != 4:
-        return None
-    import msrflute_amd.core.client as cm
-    ds = cm.train_dataset
-    if ds is None:
-        return None
-    dms = data_cfg.get("desired_max_samples", None)
-    for cid in client_ids:
-        i = store.user_pos.get(ds.user_list[cid])
-        if i is None:
-            return None
-        n = store.offsets[i + 1] - store.offsets[i]
-        if n == 0 or (dms is not None and n > dms):
-            return None
-    out = self._mega_resnet.run(store, ds, client_ids, seeds, initial_lr,
-                                self.server_arena, self.round_accums[0])
-    if out is not None:
-        self._streams_dirty = True
-        prim.perf_acc["clients"] = (prim.perf_acc.get("clients", 0)
-                                    + len(client_ids))
-    return out
-
-
-def _pool_run_fused_round_batch(self, client_ids, initial_lr, iteration,
-                                seeds):
-    """ClientPool: one _C.cnn_round per executor (on its stream) covering
-    its chunk of the round's clients.  Returns outputs or None if the
-    fused path is ineligible (caller falls back to the per-client path).
-    Eligibility is validated UP FRONT so no partial state is mutated on
-    the fallback path."""
-    prim = self.executors[0]
-    data_cfg = prim.client_config["data_config"]["train"]
-    if not _fused_round_eligible(prim, data_cfg):
-        return None
-    if getattr(self, "_mega_lstm", "missing") == "missing":
-        self._mega_lstm = None
-    if getattr(self, "_mega_resnet", "missing") == "missing":
-        self._mega_resnet = None
-    out = _try_mega_lstm_round(self, prim, data_cfg, client_ids,
-                               initial_lr, seeds)
-    if out is None:
-        out = _try_mega_resnet_round(self, prim, data_cfg, client_ids,
-                                     initial_lr, seeds)
-    if out is not None:
-        return out
-    if prim.fused_cnn is None:
-        return None
-    store = prim._get_shard_store(data_cfg)
-    if store is None or store.x[0].numel() != 784:
-        return None
-    import msrflute_amd.core.client as cm
-    ds = cm.train_dataset
-    if ds is None:
-        return None
-    dms = data_cfg.get("desired_max_samples", None)
-    for cid in client_ids:
-        i = store.user_pos.get(ds.user_list[cid])
-        if i is None:
-            return None
-        n = store.offsets[i + 1] - store.offsets[i]
-        if n == 0 or (dms is not None and n > dms):
-            return None
-
-    # cross-client MEGA round: one launch set per batch-step covering all
-    # K clients (fp32 path; bf16 keeps the per-executor fused rounds)
-    fc = prim.fused_cnn
-    if prim.client_config.get("use_mega_round", True):
-        if getattr(self, "_mega", None) is None:
-            from ..ops.fused_cnn import MegaRound
-            self._mega = MegaRound(prim.arena, fc.C, fc.bs, fc.p1, fc.p2,
-                                   prim.client_config["data_config"]["train"]
-                                   .get("max_grad_norm"),
-                                   use_bf16=fc.use_bf16)
-        if self._mega.supports(len(client_ids)):
-            out = self._mega.run(store, ds, client_ids, seeds, initial_lr,
-                                 self.server_arena, self.round_accums[0])
-            if out is not None:
-                self._streams_dirty = True
-                prim.perf_acc["clients"] = (prim.perf_acc.get("clients", 0)
-                                            + len(client_ids))
-                return out
-    for ex in self.executors[1:]:
-        if not ex._shard_store_tried:
-            ex._shard_store = store
-            ex._shard_store_tried = True
-
-    P = len(self.executors)
-    chunks = [client_ids[k::P] for k in range(P)]
-    seed_chunks = [seeds[k::P] for k in range(P)]
-    outputs = []
-    for k, (chunk, schunk) in enumerate(zip(chunks, seed_chunks)):
-        if not chunk:
-            continue
-        ex, st = self.executors[k], self.streams[k]
-        ex.round_accum_target = self.round_accums[k]
-        st.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(st):
-            out = _fused_round_impl(ex, chunk, initial_lr, schunk)
-        assert out is not None  # pre-validated above
-        outputs.extend(out)
-        self._streams_dirty = True
-    return outputs
-
-
-ClientPool.run_fused_round_batch = _pool_run_fused_round_batch
+    ex.perf_acc["clients"] = ex.perf_acc.get("clients", 0) + K
+    return round_outputs(client_ids, counts, fc.bs, ex._round_loss,
+                         ex._round_stats, ex.arena.total)

@@ -320,84 +320,52 @@ void cnn_round(torch::Tensor shard_x, torch::Tensor shard_y,
       loss_out.data_ptr<float>(), cur_stream(), use_bf16 ? 1 : 0);
 }
 
-// fused LSTM sequence recurrence (lstm_seq.hip): forward over all T
-// steps in one launch; returns (h_seq, activated gates, cell states)
+// fused LSTM sequence recurrence (lstm_seq.hip): all T steps in one
+// launch over xp [R, T, 4H] and K-stacked float4-packed hidden weights
+// (ops/lstm._pack_fwd / _pack_bwd); row r belongs to client
+// r / rows_per_client.  Forward returns (h_seq, activated gates, cell
+// states).
 std::vector<torch::Tensor> lstm_seq_fwd(torch::Tensor xp,
-                                        torch::Tensor w_hh) {
-  check_flat(xp, "xp"); check_flat(w_hh, "w_hh");
-  TORCH_CHECK(xp.dim() == 3 && xp.size(2) == 4 * 256 &&
-              w_hh.numel() == 256 * 4 * 256,
-              "fused LSTM supports hidden size 256; pass W_hh "
-              "float4-packed [H/4, 4H, 4] (ops/lstm._pack_fwd)");
-  long long B = xp.size(0), T = xp.size(1);
-  auto h_seq = torch::empty({B, T, 256}, xp.options());
-  auto gates = torch::empty({B, T, 4 * 256}, xp.options());
-  auto c_seq = torch::empty({B, T, 256}, xp.options());
-  launch_lstm_seq_fwd(xp.data_ptr<float>(), w_hh.data_ptr<float>(),
+                                        torch::Tensor w_packed_stack,
+                                        int64_t rows_per_client) {
+  check_flat(xp, "xp"); check_flat(w_packed_stack, "w_packed_stack");
+  TORCH_CHECK(xp.dim() == 3 && xp.size(2) == 4 * 256,
+              "fused LSTM supports hidden size 256: xp must be "
+              "[R, T, 4*256]");
+  long long R = xp.size(0), T = xp.size(1);
+  TORCH_CHECK(rows_per_client > 0 && R % rows_per_client == 0);
+  long long K = R / rows_per_client;
+  TORCH_CHECK(w_packed_stack.numel() == K * 256 * 4 * 256,
+              "w_packed_stack must be [K, 256/4, 4*256, 4] "
+              "(ops/lstm._pack_fwd)");
+  auto h_seq = torch::empty({R, T, 256}, xp.options());
+  auto gates = torch::empty({R, T, 4 * 256}, xp.options());
+  auto c_seq = torch::empty({R, T, 256}, xp.options());
+  launch_lstm_seq_fwd(xp.data_ptr<float>(),
+                      w_packed_stack.data_ptr<float>(),
                       h_seq.data_ptr<float>(), gates.data_ptr<float>(),
-                      c_seq.data_ptr<float>(), (int)B, (int)T, 256,
-                      cur_stream());
+                      c_seq.data_ptr<float>(), (int)R,
+                      (int)rows_per_client, (int)T, cur_stream());
   return {h_seq, gates, c_seq};
 }
 
 torch::Tensor lstm_seq_bwd(torch::Tensor gates, torch::Tensor c_seq,
-                           torch::Tensor w_hh, torch::Tensor dh_out) {
+                           torch::Tensor w_packed_stack,
+                           torch::Tensor dh_out, int64_t rows_per_client) {
   check_flat(gates, "gates"); check_flat(c_seq, "c_seq");
-  check_flat(w_hh, "w_hh"); check_flat(dh_out, "dh_out");
-  TORCH_CHECK(w_hh.numel() == 4 * 256 * 256,
-              "lstm_seq_bwd wants W_hh float4-packed [4H/4, H, 4] "
-              "(ops/lstm._pack_bwd)");
-  long long B = gates.size(0), T = gates.size(1);
-  auto dg = torch::empty_like(gates);
-  launch_lstm_seq_bwd(gates.data_ptr<float>(), c_seq.data_ptr<float>(),
-                      w_hh.data_ptr<float>(), dh_out.data_ptr<float>(),
-                      dg.data_ptr<float>(), (int)B, (int)T, 256,
-                      cur_stream());
-  return dg;
-}
-
-// batched (cross-client) LSTM recurrence: xp [R, T, 4H], K-stacked
-// transposed hidden weights [K, H, 4H]; row r belongs to client
-// r / rows_per_client (Shakespeare mega round)
-std::vector<torch::Tensor> lstm_seq_fwd_b(torch::Tensor xp,
-                                          torch::Tensor w_hh_t_stack,
-                                          int64_t rows_per_client) {
-  check_flat(xp, "xp"); check_flat(w_hh_t_stack, "w_hh_t_stack");
-  TORCH_CHECK(xp.dim() == 3 && xp.size(2) == 4 * 256,
-              "xp must be [R, T, 4*256]");
-  long long R = xp.size(0), T = xp.size(1);
-  TORCH_CHECK(rows_per_client > 0 && R % rows_per_client == 0);
-  long long K = R / rows_per_client;
-  TORCH_CHECK(w_hh_t_stack.numel() == K * 256 * 4 * 256,
-              "w_hh_t_stack must be [K, 256, 4*256]");
-  auto h_seq = torch::empty({R, T, 256}, xp.options());
-  auto gates = torch::empty({R, T, 4 * 256}, xp.options());
-  auto c_seq = torch::empty({R, T, 256}, xp.options());
-  launch_lstm_seq_fwd_b(xp.data_ptr<float>(),
-                        w_hh_t_stack.data_ptr<float>(),
-                        h_seq.data_ptr<float>(), gates.data_ptr<float>(),
-                        c_seq.data_ptr<float>(), (int)R,
-                        (int)rows_per_client, (int)T, cur_stream());
-  return {h_seq, gates, c_seq};
-}
-
-torch::Tensor lstm_seq_bwd_b(torch::Tensor gates, torch::Tensor c_seq,
-                             torch::Tensor w_hh_stack,
-                             torch::Tensor dh_out,
-                             int64_t rows_per_client) {
-  check_flat(gates, "gates"); check_flat(c_seq, "c_seq");
-  check_flat(w_hh_stack, "w_hh_stack"); check_flat(dh_out, "dh_out");
+  check_flat(w_packed_stack, "w_packed_stack");
+  check_flat(dh_out, "dh_out");
   long long R = gates.size(0), T = gates.size(1);
   TORCH_CHECK(rows_per_client > 0 && R % rows_per_client == 0);
   long long K = R / rows_per_client;
-  TORCH_CHECK(w_hh_stack.numel() == K * 4 * 256 * 256,
-              "w_hh_stack must be [K, 4*256, 256]");
+  TORCH_CHECK(w_packed_stack.numel() == K * 4 * 256 * 256,
+              "w_packed_stack must be [K, 4*256/4, 256, 4] "
+              "(ops/lstm._pack_bwd)");
   auto dg = torch::empty_like(gates);
-  launch_lstm_seq_bwd_b(gates.data_ptr<float>(), c_seq.data_ptr<float>(),
-                        w_hh_stack.data_ptr<float>(),
-                        dh_out.data_ptr<float>(), dg.data_ptr<float>(),
-                        (int)R, (int)rows_per_client, (int)T,
-                        cur_stream());
+  launch_lstm_seq_bwd(gates.data_ptr<float>(), c_seq.data_ptr<float>(),
+                      w_packed_stack.data_ptr<float>(),
+                      dh_out.data_ptr<float>(), dg.data_ptr<float>(),
+                      (int)R, (int)rows_per_client, (int)T, cur_stream());
   return dg;
 }
 
@@ -838,8 +806,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("cnn_epoch", &cnn_epoch);
   m.def("cnn_round", &cnn_round);
   m.def("lstm_seq_fwd", &lstm_seq_fwd);
-  m.def("lstm_seq_fwd_b", &lstm_seq_fwd_b);
-  m.def("lstm_seq_bwd_b", &lstm_seq_bwd_b);
   m.def("gru_seq_fwd", &gru_seq_fwd);
   m.def("gru_seq_bwd", &gru_seq_bwd);
   m.def("lstm_seq_bwd", &lstm_seq_bwd);

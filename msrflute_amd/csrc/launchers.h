@@ -79,20 +79,15 @@ void launch_quant_bin_mask(float* x, long long n, const float* min_t,
 void launch_gru_gates(const float* g_i, const float* g_h, const float* h,
                       float* out, int B, int H, hipStream_t s);
 
-// lstm_seq.hip
-void launch_lstm_seq_fwd(const float* xp, const float* w_hh_t, float* h_seq,
-                         float* gates, float* c_seq, int B, int T, int H,
-                         hipStream_t s);
+// lstm_seq.hip — K-stacked packed W_hh; row r of the R rows belongs to
+// client r / rows_per_client (K = 1, rows_per_client = R: one model)
+void launch_lstm_seq_fwd(const float* xp, const float* w_hh_t_stack,
+                         float* h_seq, float* gates, float* c_seq, int R,
+                         int rows_per_client, int T, hipStream_t s);
 void launch_lstm_seq_bwd(const float* gates, const float* c_seq,
-                         const float* w_hh, const float* dh_out,
-                         float* dg_pre, int B, int T, int H, hipStream_t s);
-void launch_lstm_seq_fwd_b(const float* xp, const float* w_hh_t_stack,
-                           float* h_seq, float* gates, float* c_seq, int R,
-                           int rows_per_client, int T, hipStream_t s);
-void launch_lstm_seq_bwd_b(const float* gates, const float* c_seq,
-                           const float* w_hh_stack, const float* dh_out,
-                           float* dg_pre, int R, int rows_per_client, int T,
-                           hipStream_t s);
+                         const float* w_hh_stack, const float* dh_out,
+                         float* dg_pre, int R, int rows_per_client, int T,
+                         hipStream_t s);
 
 // gru_seq.hip
 void launch_gru_seq_fwd(const float* gi, const float* whh_t,

@@ -13,12 +13,14 @@ not torch's — same distribution, different bits).
 
 from __future__ import annotations
 
+from itertools import accumulate
 from typing import Optional
 
 import torch
 
 from . import HAS_EXT, _C
 from .arena import ParameterArena
+from .mega_round import plan_round, round_outputs
 
 # expected parameter layout of the flagship CNN
 # (experiments/cv_cnn_femnist/model.py)
@@ -172,30 +174,20 @@ class MegaRound:
         return K <= self.k_cap
 
     def run(self, store, ds, client_ids, seeds, initial_lr: float,
-            server_arena: ParameterArena, round_accum: torch.Tensor):
+            server_arena: ParameterArena, round_accum: torch.Tensor,
+            desired_max_samples=None):
         """Returns the per-client outputs list [(cid, meta), ...] or None
-        if a client is missing from the device shard store."""
-        import time as _time
+        (nothing touched) if the round is not eligible (plan_round)."""
         K = len(client_ids)
         if K == 0 or K > self.k_cap:
             return None
-        counts, row_bases, order_offs, orders = [], [], [], []
-        off = 0
-        for cid, seed in zip(client_ids, seeds):
-            user = ds.user_list[cid]
-            i = store.user_pos.get(user)
-            if i is None:
-                return None
-            lo, hi = store.offsets[i], store.offsets[i + 1]
-            n = hi - lo
-            if n == 0:
-                return None
-            torch.manual_seed(seed & 0x7FFFFFFFFFFF)
-            orders.append(torch.randperm(n))
-            counts.append(n)
-            row_bases.append(lo)
-            order_offs.append(off)
-            off += n
+        plan = plan_round(store, ds.user_list, client_ids, seeds,
+                          desired_max_samples)
+        if plan is None:
+            return None
+        counts, row_bases, orders = plan
+        off = sum(counts)
+        order_offs = [0] + list(accumulate(counts))[:-1]
         self._ensure(K)
         dev = self.arena.device
         orders_cat = torch.cat(orders)
@@ -235,19 +227,5 @@ class MegaRound:
             round_accum, self.work_f, self.work_i, self.work_b, self.work_d,
             self.lr_t, self.max_norm, self.p1, self.p2,
             self.stats_out, self.loss_out, self.use_bf16)
-        now = _time.time()
-        outputs = []
-        for k, cid in enumerate(client_ids):
-            n_batches = (counts[k] + self.bs - 1) // self.bs
-            outputs.append((cid, {
-                "cs": {"setup": 0.0, "training": 0.0, "full cost": 0.0,
-                       "dataloader": 0.0},
-                "ns": counts[k],
-                "pl": {"weight": float(counts[k]), "grad": None,
-                       "pooled": True},
-                "_lazy": (self.loss_out[k].reshape(()),
-                          self.stats_out[2 * k: 2 * k + 2],
-                          n_batches * self.arena.total),
-                "ts": now,
-            }))
-        return outputs
+        return round_outputs(client_ids, counts, self.bs, self.loss_out,
+                             self.stats_out, self.arena.total)

@@ -21,38 +21,49 @@ from . import HAS_EXT, _C
 
 
 def _pack_fwd(w_hh):
-    """[4H, H] -> float4-packed [H/4, 4H, 4]: element (kk, j, d) =
-    W_hh[j, 4kk+d], so the forward kernel's per-step weight read is one
-    b128 per 4 hidden units (4x fewer loads in the latency-bound loop)."""
-    H4, H = w_hh.shape
-    return w_hh.t().reshape(H // 4, 4, H4).permute(0, 2, 1).contiguous()
+    """[..., 4H, H] -> float4-packed [..., H/4, 4H, 4]: element
+    (kk, j, d) = W_hh[j, 4kk+d], so the forward kernel's per-step weight
+    read is one b128 per 4 hidden units (4x fewer loads in the
+    latency-bound loop).  Leading dims (the client stack) pass through."""
+    *lead, H4, H = w_hh.shape
+    return w_hh.transpose(-1, -2).reshape(*lead, H // 4, 4, H4) \
+        .transpose(-1, -2).contiguous()
 
 
 def _pack_bwd(w_hh):
-    """[4H, H] -> float4-packed [4H/4, H, 4]: element (jg, h, d) =
-    W_hh[4jg+d, h] (the backward dot's b128 form)."""
-    H4, H = w_hh.shape
-    return w_hh.reshape(H4 // 4, 4, H).permute(0, 2, 1).contiguous()
+    """[..., 4H, H] -> float4-packed [..., 4H/4, H, 4]: element
+    (jg, h, d) = W_hh[4jg+d, h] (the backward dot's b128 form)."""
+    *lead, H4, H = w_hh.shape
+    return w_hh.reshape(*lead, H4 // 4, 4, H).transpose(-1, -2).contiguous()
 
 
 class _LSTMSeq(torch.autograd.Function):
+    """One LSTM layer's recurrence over xp [R, T, 4H] with K-stacked
+    hidden weights w_hh_stack [K, 4H, H]: row r uses client
+    r // rows_per_client's weights (K = 1: one model, rows_per_client = R)."""
+
     @staticmethod
-    def forward(ctx, xp, w_hh):
+    def forward(ctx, xp, w_hh_stack, rows_per_client):
         h_seq, gates, c_seq = _C.lstm_seq_fwd(
-            xp.contiguous(), _pack_fwd(w_hh))
-        ctx.save_for_backward(gates, c_seq, w_hh, h_seq)
+            xp.contiguous(), _pack_fwd(w_hh_stack), rows_per_client)
+        ctx.save_for_backward(gates, c_seq, w_hh_stack, h_seq)
+        ctx.rows_per_client = rows_per_client
         return h_seq
 
     @staticmethod
     def backward(ctx, dh):
-        gates, c_seq, w_hh, h_seq = ctx.saved_tensors
-        dg = _C.lstm_seq_bwd(gates, c_seq, _pack_bwd(w_hh),
-                             dh.contiguous())
-        B, T, H = h_seq.shape
-        h_prev = torch.cat([h_seq.new_zeros(B, 1, H), h_seq[:, :-1]], dim=1)
-        # dW_hh = sum_t dgates_t^T h_{t-1} : one GEMM over the stacked steps
-        dw_hh = dg.reshape(-1, 4 * H).t().mm(h_prev.reshape(-1, H))
-        return dg, dw_hh
+        gates, c_seq, w_hh_stack, h_seq = ctx.saved_tensors
+        rpc = ctx.rows_per_client
+        dg = _C.lstm_seq_bwd(gates, c_seq, _pack_bwd(w_hh_stack),
+                             dh.contiguous(), rpc)
+        R, T, H = h_seq.shape
+        K = R // rpc
+        h_prev = torch.cat([h_seq.new_zeros(R, 1, H), h_seq[:, :-1]], dim=1)
+        # dW_hh[k] = sum_t dgates_t^T h_{t-1} over client k's rows: one
+        # batched GEMM over the stacked steps
+        dw_hh = torch.bmm(dg.view(K, rpc * T, 4 * H).transpose(1, 2),
+                          h_prev.view(K, rpc * T, H))
+        return dg, dw_hh, None
 
 
 class FusedLSTM(nn.Module):
@@ -88,7 +99,7 @@ class FusedLSTM(nn.Module):
             w_hh = getattr(self, f"weight_hh_l{k}")
             b = getattr(self, f"bias_ih_l{k}") + getattr(self, f"bias_hh_l{k}")
             xp = h.matmul(w_ih.t()) + b
-            h = _LSTMSeq.apply(xp, w_hh)
+            h = _LSTMSeq.apply(xp, w_hh.unsqueeze(0), x.shape[0])
         return h, None
 
 

@@ -59,3 +59,14 @@ def test_unshuffled_loader_consumes_no_rng():
     xs = torch.cat([b["x"] for b in dl.create_loader()])
     expect = torch.tensor(blob["user_data"]["u0"]["x"])[order_direct]
     assert torch.equal(xs.cpu(), expect)
+
+
+def test_pack_stack_equals_stacked_2d_packs():
+    """The K-stacked packs the recurrence kernels index per client are
+    exactly the per-client 2-D packs, stacked."""
+    H = 8
+    w = torch.randn(2, 4 * H, H)
+    for pack in (_pack_fwd, _pack_bwd):
+        p = pack(w)
+        assert p.is_contiguous()
+        assert torch.equal(p, torch.stack([pack(w[0]), pack(w[1])]))

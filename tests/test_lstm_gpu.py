@@ -34,6 +34,39 @@ def test_fused_lstm_matches_nn_lstm():
             (n1, (p1.grad - p2.grad).abs().max().item())
 
 
+@pytest.mark.gpu
+def test_lstm_seq_stacked_matches_single_client():
+    """The recurrence over K = 2 stacked clients (3 rows each, DIFFERENT
+    W_hh) against a K = 1 call on each client alone.  The kernels are
+    deterministic and a row's arithmetic does not depend on K, so h_seq
+    and the gate gradients must be bit-equal — anything else is a row ->
+    client indexing bug.  dW_hh goes through a differently batched GEMM."""
+    from msrflute_amd.ops.lstm import _LSTMSeq
+
+    torch.manual_seed(17)
+    K, rpc, T, H = 2, 3, 5, 256
+    # both clients see the SAME inputs, so only W_hh tells them apart
+    xp = torch.randn(rpc, T, 4 * H, device="cuda").repeat(K, 1, 1) \
+        .requires_grad_(True)
+    w = (torch.randn(K, 4 * H, H, device="cuda") / 16).requires_grad_(True)
+    dh = torch.randn(K * rpc, T, H, device="cuda")
+
+    h = _LSTMSeq.apply(xp, w, rpc)
+    dxp, dw = torch.autograd.grad(h, [xp, w], dh)
+    for k in range(K):
+        rows = slice(k * rpc, (k + 1) * rpc)
+        xp_k = xp[rows].detach().clone().requires_grad_(True)
+        w_k = w[k:k + 1].detach().clone().requires_grad_(True)
+        h_k = _LSTMSeq.apply(xp_k, w_k, rpc)
+        dxp_k, dw_k = torch.autograd.grad(h_k, [xp_k, w_k], dh[rows])
+        assert torch.equal(h[rows], h_k), k
+        assert torch.equal(dxp[rows], dxp_k), k
+        assert torch.allclose(dw[k], dw_k[0], rtol=1e-3, atol=1e-4), \
+            (k, (dw[k] - dw_k[0]).abs().max().item())
+    # each client's rows really ran that client's weights
+    assert not torch.equal(h[:rpc], h[rpc:])
+
+
 def test_fused_lstm_cpu_fallback_is_exact():
     from msrflute_amd.ops.lstm import FusedLSTM
     torch.manual_seed(5)

@@ -43,13 +43,13 @@ whh = torch.randn(4*H, H, device="cuda")
 torch.cuda.synchronize(); t0=time.time()
 for _ in range(N):
     from msrflute_amd.ops.lstm import _pack_fwd, _pack_bwd
-    h_seq, gates, c_seq = _C.lstm_seq_fwd(xp, _pack_fwd(whh))
+    h_seq, gates, c_seq = _C.lstm_seq_fwd(xp, _pack_fwd(whh), B)
 torch.cuda.synchronize()
 print(f"lstm_seq_fwd per call: {(time.time()-t0)/N*1000:.3f} ms (T={T})")
 dh = torch.randn_like(h_seq)
 torch.cuda.synchronize(); t0=time.time()
 for _ in range(N):
-    dg = _C.lstm_seq_bwd(gates, c_seq, _pack_bwd(whh), dh)
+    dg = _C.lstm_seq_bwd(gates, c_seq, _pack_bwd(whh), dh, B)
 torch.cuda.synchronize()
 print(f"lstm_seq_bwd per call: {(time.time()-t0)/N*1000:.3f} ms")
 
@@ -63,6 +63,6 @@ if g is not None:
     gc.set_lr(0.8)
     torch.cuda.synchronize(); t0=time.time()
     for _ in range(N):
-        g.run(x, y)
+        g.run_batch(x, y)
     torch.cuda.synchronize()
     print(f"graph replay per batch: {(time.time()-t0)/N*1000:.3f} ms")

@@ -14,7 +14,7 @@ def run_serial(n_iter=10):
     torch.cuda.synchronize(); t0 = time.time()
     for _ in range(n_iter):
         for k in range(NS):
-            _C.lstm_seq_fwd(xps[k], whts[k])
+            _C.lstm_seq_fwd(xps[k], whts[k], B)
     torch.cuda.synchronize()
     return (time.time()-t0)/n_iter*1000
 
@@ -23,7 +23,7 @@ def run_streams(n_iter=10):
     for _ in range(n_iter):
         for k in range(NS):
             with torch.cuda.stream(streams[k]):
-                _C.lstm_seq_fwd(xps[k], whts[k])
+                _C.lstm_seq_fwd(xps[k], whts[k], B)
         for st in streams:
             torch.cuda.current_stream().wait_stream(st)
     torch.cuda.synchronize()
