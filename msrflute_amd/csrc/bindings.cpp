@@ -185,7 +185,6 @@ static CnnWorkspace slice_ws(torch::Tensor& work_f, torch::Tensor& work_i,
   ws.a2 = f;            f += (long long)B * 9216;
   ws.z3 = f;            f += (long long)B * 128;
   ws.a3 = f;            f += (long long)B * 128;
-  ws.dlogits = f;       f += (long long)B * C;
   ws.dz3 = f;           f += (long long)B * 128;
   ws.da2 = f;           f += (long long)B * 9216;
   ws.dz2 = f;           f += (long long)B * 36864;
@@ -193,6 +192,9 @@ static CnnWorkspace slice_ws(torch::Tensor& work_f, torch::Tensor& work_i,
   ws.wsl = f;           f += (long long)B * 18432;  // split-K partial slab
   ws.w2t = f;           f += 18432;
   ws.w2rot = f;         f += 18432;
+  // B*C need not be a multiple of 4 floats: dlogits goes last so that the
+  // buffers the conv2 kernels move as float4 stay 16 B aligned
+  ws.dlogits = f;       f += (long long)B * C;
   TORCH_CHECK(f - work_f.data_ptr<float>() <= work_f.numel(),
               "float workspace too small");
   TORCH_CHECK(work_i.numel() >= B, "int workspace too small");
@@ -559,12 +561,10 @@ std::vector<torch::Tensor> dbg_conv2_bwd_w_mfma(torch::Tensor dz2,
   int bs = rows_per_client(B, K);
   TORCH_CHECK(dz2.numel() >= B * 36864 && a1.numel() >= B * 21632);
   auto slab = torch::empty({B * 18432}, dz2.options());
-  auto dz2t = torch::empty({B * 36864}, dz2.options());
   auto dw2 = torch::empty({K * 18432}, dz2.options());
   auto db2 = torch::empty({K * 64}, dz2.options());
   launch_conv2_bwd_w_mfma(dz2.data_ptr<float>(), a1.data_ptr<float>(),
-                          bs, (int)K, dz2t.data_ptr<float>(),
-                          slab.data_ptr<float>(),
+                          bs, (int)K, slab.data_ptr<float>(),
                           dw2.data_ptr<float>(), db2.data_ptr<float>(),
                           cur_stream());
   return {dw2, db2};
@@ -691,7 +691,6 @@ void cnn_round_mega(torch::Tensor shard_x, torch::Tensor shard_y,
   float* a2 = take((long long)G * 9216);
   float* z3 = take((long long)G * 128);
   float* a3 = take((long long)G * 128);
-  float* dlg = take((long long)G * C);
   float* dz3 = take((long long)G * 128);
   float* da2 = take((long long)G * 9216);
   float* dz2 = take((long long)G * 36864);
@@ -699,6 +698,7 @@ void cnn_round_mega(torch::Tensor shard_x, torch::Tensor shard_y,
   float* w2t = take((long long)K * 18432);
   float* w2rot = take((long long)K * 18432);
   float* slab = take((long long)G * 18432);
+  float* dlg = take((long long)G * C);  // last: keeps the rest 16 B aligned
   TORCH_CHECK(f - work_f.data_ptr<float>() <= work_f.numel(),
               "mega float workspace too small");
   TORCH_CHECK(work_i.numel() >= G, "mega int workspace too small");
@@ -771,6 +771,8 @@ void mega_pseudo_accum(torch::Tensor grads_stack, torch::Tensor server,
 }
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
+  // output rows per block of the f32 conv2 forward (its slab seams)
+  m.attr("CONV2_FWD_SLAB_ROWS") = CONV2_FWD_SLAB_ROWS;
   m.def("cnn_round_mega", &cnn_round_mega);
   m.def("mega_clip_sgd", &mega_clip_sgd);
   m.def("mega_pseudo_accum", &mega_pseudo_accum);

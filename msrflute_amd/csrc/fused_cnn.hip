@@ -14,8 +14,8 @@
 // batch-step trains ALL K sampled clients, the super-batch dimension is
 // G = K*bs rows (row g belongs to client k = g/bs), every kernel takes
 // per-client parameter/gradient stacks (params_stack[k*P ..]), and grids
-// scale by K — conv2 fwd is K*bs*9 = 1800 blocks at the benchmark shape,
-// where a per-client grid (180 blocks) underfills the 256-CU chip.  The
+// scale by K — conv2 fwd is K*bs*6 = 1200 blocks at the benchmark shape,
+// where a per-client grid (120 blocks) underfills the 256-CU chip.  The
 // per-client epoch (launch_cnn_epoch) launches the same kernels at K = 1
 // with bs := the batch's actual row count and the client's own arena as
 // the stack.  Only the four ops that read per-client metadata (gather,
@@ -50,9 +50,6 @@
 // Fragment maps: A[i=l&15][k=l>>4], B[k=l>>4][j=l&15] one f32 VGPR each;
 // D[row=(l>>4)*4+r][col=l&15], 4 f32 per lane.
 typedef __attribute__((ext_vector_type(4))) float f32x4;
-
-#define MC2F_LD 585  /* padded f32 LDS row stride (585 %% 32 = 9, odd ->
-                        conflict-free 16-lane fragment groups) */
 
 // per-row helpers: g in [0, K*bs), k = g / bs, b = g % bs
 __device__ __forceinline__ int mega_Bk(const long long* counts, int k,
@@ -188,50 +185,102 @@ __global__ void k_w2_layouts_mb(const float* __restrict__ params,
   }
 }
 
-// conv2 forward (f32 MFMA): grid = G * 9 blocks; per-block client k
+// Lane constants of the (channel, kh, kw) k-decomposition shared by the
+// conv2 forward and backward-data implicit GEMMs.  The k index of lane
+// group kc in MFMA step s is 4s + kc and decomposes with period 9, so
+// over 36 k (9 steps, 4 channels) step j touches channel (4j+kc)/9 and
+// tap (4j+kc)%9: nine loop-invariant LDS offsets per lane, and the
+// k-loop only adds a 4-channel stride.  cs = staged channel stride,
+// tap = signed (kh, kw) step of the staged image (row stride rs).
+__device__ __forceinline__ void conv2_tap_offsets(int kc, int cs, int rs,
+                                                  int sgn, int off[9]) {
+  #pragma unroll
+  for (int j = 0; j < 9; ++j) {
+    int q = 4 * j + kc, c = q / 9, rem = q % 9;
+    off[j] = c * cs + sgn * ((rem / 3) * rs + rem % 3);
+  }
+}
+
+// conv2 forward (f32 MFMA), implicit GEMM straight from raw activations.
+// grid = G * C2F_SLABS; a block owns a slab of CONV2_FWD_SLAB_ROWS output
+// rows (96 positions x 64 co) of one image and stages only the rows+2
+// input rows of each ci it needs (19.5 KB, one 624 B run per plane), so
+// an image's a1 is filled ~1.5x instead of 9x.  Wave w owns a 3 x 2 block
+// of 16x16 accumulators (m-tiles 3*(w>>1).., co half w&1): each W2
+// fragment (one global load per k-step from w2t) feeds 3 MFMAs, each a1
+// fragment 2, and consecutive MFMAs are independent.  Every output's k
+// order is (ci,kh,kw) ascending from 0, bias and ReLU after, as before.
+#define C2F_ROWS CONV2_FWD_SLAB_ROWS
+#define C2F_SLABS (24 / C2F_ROWS)
+#define C2F_CS ((C2F_ROWS + 2) * 26)  /* staged floats per ci plane */
+static_assert(24 % C2F_ROWS == 0 && (C2F_ROWS * 24) % 96 == 0 &&
+              C2F_CS % 4 == 0 && C2F_CS / 4 <= 64,
+              "conv2 fwd slab: 6 m-tiles per block, float4 plane copies");
 __global__ __launch_bounds__(256)
 void k_conv2_fwd_mfma_mb(const float* __restrict__ a1,
                          const float* __restrict__ w2t_stack,
                          const float* __restrict__ params, long long P,
                          long long ob2, int bs, int K,
                          float* __restrict__ r2) {
-  __shared__ float lds[32 * 676];
-  long long g = blockIdx.x / 9;
-  int mt = blockIdx.x % 9;
+  __shared__ __attribute__((aligned(16))) float lds[32 * C2F_CS];
+  long long g = blockIdx.x / C2F_SLABS;
+  int sl = blockIdx.x % C2F_SLABS;
   int k = (int)(g / bs);
-  const float* src = a1 + g * 21632;
-  for (int i = threadIdx.x; i < 21632; i += 256) lds[i] = src[i];
-  __syncthreads();
-  const float* w2t = w2t_stack + (long long)k * 18432;
-  const float* b2 = params + (long long)k * P + ob2;
   int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  int m = mt * 64 + w * 16 + (lane & 15);
-  int yy = m / 24, xx = m % 24;
-  int kc = lane >> 4;
-  f32x4 acc[4] = {f32x4{0,0,0,0}, f32x4{0,0,0,0},
-                  f32x4{0,0,0,0}, f32x4{0,0,0,0}};
-  #pragma unroll 4
-  for (int k0 = 0; k0 < 288; k0 += 4) {
-    int kk = k0 + kc;
-    int ci = kk / 9, rem = kk % 9, kh = rem / 3, kw = rem % 3;
-    float a = lds[ci * 676 + (yy + kh) * 26 + xx + kw];
-    const float* wrow = w2t + (long long)kk * 64 + (lane & 15);
+  // wave w copies planes w, w+4, ..: lanes 0..38 move one float4 each
+  const float4* src = reinterpret_cast<const float4*>(
+      a1 + g * 21632 + sl * (C2F_ROWS * 26));
+  if (lane < C2F_CS / 4)
+    for (int ci = w; ci < 32; ci += 4)
+      reinterpret_cast<float4*>(lds)[ci * (C2F_CS / 4) + lane] =
+          src[ci * 169 + lane];
+  __syncthreads();
+  int il = lane & 15, kc = lane >> 4;
+  int nh = w & 1, mh = w >> 1;
+  int off[9], base[3];
+  conv2_tap_offsets(kc, C2F_CS, 26, 1, off);
+  #pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    int m = (mh * 3 + i) * 16 + il;
+    base[i] = (m / 24) * 26 + m % 24;
+  }
+  const float* wp = w2t_stack + (long long)k * 18432 + kc * 64 + nh * 32 + il;
+  f32x4 acc[3][2];
+  #pragma unroll
+  for (int i = 0; i < 3; ++i)
+    acc[i][0] = acc[i][1] = f32x4{0, 0, 0, 0};
+  for (int t = 0; t < 8; ++t) {
+    const float* lt = lds + t * 4 * C2F_CS;
+    const float* wt = wp + t * 36 * 64;
     #pragma unroll
-    for (int nt = 0; nt < 4; ++nt) {
-      float bv = wrow[nt * 16];
-      acc[nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, bv, acc[nt], 0, 0, 0);
+    for (int j = 0; j < 9; ++j) {
+      float b0 = wt[j * 256], b1 = wt[j * 256 + 16];
+      #pragma unroll
+      for (int i = 0; i < 3; ++i) {
+        float a = lt[base[i] + off[j]];
+        acc[i][0] =
+            __builtin_amdgcn_mfma_f32_16x16x4f32(a, b0, acc[i][0], 0, 0, 0);
+        acc[i][1] =
+            __builtin_amdgcn_mfma_f32_16x16x4f32(a, b1, acc[i][1], 0, 0, 0);
+      }
     }
   }
-  int om = mt * 64 + w * 16 + (lane >> 4) * 4;
-  int cl = lane & 15;
+  const float* b2 = params + (long long)k * P + ob2;
   #pragma unroll
-  for (int r = 0; r < 4; ++r)
+  for (int n = 0; n < 2; ++n) {
+    int co = nh * 32 + n * 16 + il;
+    float bias = b2[co];
     #pragma unroll
-    for (int nt = 0; nt < 4; ++nt) {
-      int co = nt * 16 + cl;
-      float v = acc[nt][r] + b2[co];
-      r2[(g * 64 + co) * 576 + om + r] = v > 0.f ? v : 0.f;
+    for (int i = 0; i < 3; ++i) {
+      int om = sl * (C2F_ROWS * 24) + (mh * 3 + i) * 16 + kc * 4;
+      float4 v;
+      v.x = acc[i][n][0] + bias; v.y = acc[i][n][1] + bias;
+      v.z = acc[i][n][2] + bias; v.w = acc[i][n][3] + bias;
+      v.x = v.x > 0.f ? v.x : 0.f; v.y = v.y > 0.f ? v.y : 0.f;
+      v.z = v.z > 0.f ? v.z : 0.f; v.w = v.w > 0.f ? v.w : 0.f;
+      *reinterpret_cast<float4*>(r2 + (g * 64 + co) * 576 + om) = v;
     }
+  }
 }
 
 // maxpool 2x2 + dropout(p1) of pool cell i, whose 2x2 window starts at
@@ -672,68 +721,125 @@ __global__ void k_pool_drop_bwd_mb(const float* __restrict__ da2,
   }
 }
 
-__global__ void k_dz2_transpose_mb(const float* __restrict__ dz2, int bs,
-                                   int K, float* __restrict__ dz2t) {
-  long long total = (long long)K * bs * 36864;
-  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
-       i < total; i += (long long)gridDim.x * blockDim.x) {
-    long long g = i / 36864;
-    int r = (int)(i % 36864), o = r / 64, co = r % 64;
-    dz2t[i] = dz2[(g * 64 + co) * 576 + o];
-  }
-}
-
-// conv2 backward weights (f32 MFMA): 32x32 (co x n) tiles, K=576
-// staged in TWO 288-deep chunks so the live LDS is 74 KB -> 2
-// blocks/CU (a one-shot 576-deep stage was 149 KB -> 1 block/CU and
-// measured WORSE than the 64-row form).  A = dz2t rows; B = im2col^T.
-// grid = G * 18 (2 co-halves x 9 n-blocks); one accumulator per wave.
-#define MC2FW_LD 289  /* 289 %% 32 = 1 -> conflict-free fragment groups */
-__global__ __launch_bounds__(256)
-void k_conv2_bwd_w_mfma_mb(const float* __restrict__ dz2t,
+// conv2 backward weights (f32 MFMA): per image, dw[co][n] = sum over the
+// 576 output positions o of dz2[co][o] * a1[ci(n)][(y+kh)*26 + x+kw].
+// grid = G * 9, 128 threads; a block owns all 64 co x 32 n columns and
+// walks o in chunks of C2W_ROWS output rows.  Per chunk it stages the
+// dz2 rows in their native [co][o] layout (8 lanes x float4 = one 128 B
+// line per row piece) and the raw rows+2 a1 rows of the <= 5 ci planes
+// its 32 columns touch; no im2col tile and no transposed copy of dz2.
+// The B address is o + 2*(o/24) plus a per-lane (ci,kh,kw) constant: the
+// k-loop is unrolled by one 24-wide output row, so every offset is an
+// immediate.  Wave w owns a 2 x 2 block of accumulators (co 32w..32w+31),
+// each dz2 / a1 fragment feeds 2 MFMAs.  Each image's partial runs over o
+// ascending from 0; k_conv2_bwd_w_fold_mb then sums rows b ascending.
+#define C2W_ROWS 4                      /* output rows per staged chunk */
+#define C2W_OC (C2W_ROWS * 24)          /* k (= o) values per chunk */
+#define C2W_LD (C2W_OC + 2)             /* 98 %% 32 = 2: the 16 co x 2 kc of
+                                           a 32-lane group hit 32 banks */
+#define C2W_PS ((C2W_ROWS + 2) * 26)    /* staged floats per a1 plane */
+static_assert(24 % C2W_ROWS == 0 && C2W_OC % 32 == 0 && C2W_PS <= 256,
+              "conv2 bwd_w chunk: whole rows, whole 128 B row pieces, an a1 "
+              "plane in two passes of the 128 threads");
+__global__ __launch_bounds__(128)
+void k_conv2_bwd_w_mfma_mb(const float* __restrict__ dz2,
                            const float* __restrict__ a1, int bs, int K,
                            float* __restrict__ slab) {
-  __shared__ float dzl[32 * MC2FW_LD];
-  __shared__ float imt[32 * MC2FW_LD];
-  int blk = blockIdx.x % 18;
-  int ch = blk / 9, nb = blk % 9;
-  long long g = blockIdx.x / 18;
-  const float* dzb = dz2t + g * 36864;   // [o][co] layout
+  __shared__ __attribute__((aligned(16))) float dzl[64 * C2W_LD];
+  __shared__ float apl[5 * C2W_PS];
+  int nb = blockIdx.x % 9;
+  long long g = blockIdx.x / 9;
+  const float* dzb = dz2 + g * 36864;
   const float* a1b = a1 + g * 21632;
   int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   int il = lane & 15, kc = lane >> 4;
-  int csub = w & 1, nt = w >> 1;
-  f32x4 acc = {0, 0, 0, 0};
-  for (int c = 0; c < 2; ++c) {
-    int obase = c * 288;
+  int ci0 = nb * 32 / 9;
+  int npl = 32 - ci0 < 5 ? 32 - ci0 : 5;
+  int aoff[2], boff[2];
+  #pragma unroll
+  for (int q = 0; q < 2; ++q) {
+    aoff[q] = (w * 32 + q * 16 + il) * C2W_LD + kc;
+    int n = nb * 32 + q * 16 + il;
+    int ci = n / 9, rem = n % 9;
+    boff[q] = (ci - ci0) * C2W_PS + (rem / 3) * 26 + rem % 3 + kc;
+  }
+  f32x4 acc[2][2];
+  acc[0][0] = acc[0][1] = acc[1][0] = acc[1][1] = f32x4{0, 0, 0, 0};
+  int sub = threadIdx.x & 7, r0 = threadIdx.x >> 3;
+  // The next chunk's global loads are issued before the current chunk's
+  // MFMAs and held in registers, so their latency hides behind the
+  // matrix work; only the register -> LDS copy sits between barriers.
+  float4 pdz[4][C2W_OC / 32];
+  float pa[5][2];
+  auto fetch = [&](int c) {
+    #pragma unroll
+    for (int it = 0; it < 4; ++it) {
+      const float4* sp = reinterpret_cast<const float4*>(
+          dzb + (r0 + 16 * it) * 576 + c * C2W_OC);
+      #pragma unroll
+      for (int u = 0; u < C2W_OC / 32; ++u) pdz[it][u] = sp[sub + 8 * u];
+    }
+    #pragma unroll
+    for (int p = 0; p < 5; ++p) {
+      const float* sp = a1b + (ci0 + p) * 676 + c * (C2W_ROWS * 26);
+      #pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        int j = threadIdx.x + 128 * h;
+        pa[p][h] = (p < npl && j < C2W_PS) ? sp[j] : 0.f;
+      }
+    }
+  };
+  fetch(0);
+  for (int c = 0; c < 24 / C2W_ROWS; ++c) {
     __syncthreads();
-    for (int i = threadIdx.x; i < 32 * 288; i += 256) {
-      // thread-consecutive co -> 128 B contiguous dz2t reads per o
-      int o = obase + i / 32, co = i % 32;
-      dzl[co * MC2FW_LD + (o - obase)] = dzb[o * 64 + ch * 32 + co];
+    #pragma unroll
+    for (int it = 0; it < 4; ++it) {
+      float* dp = dzl + (r0 + 16 * it) * C2W_LD;
+      #pragma unroll
+      for (int u = 0; u < C2W_OC / 32; ++u) {
+        float4 v = pdz[it][u];
+        float2* d2 = reinterpret_cast<float2*>(dp + 4 * (sub + 8 * u));
+        d2[0] = float2{v.x, v.y};
+        d2[1] = float2{v.z, v.w};
+      }
     }
-    for (int i = threadIdx.x; i < 32 * 288; i += 256) {
-      int nr = i / 288, o = obase + i % 288;
-      int n = nb * 32 + nr;
-      int ci = n / 9, rem = n % 9, kh = rem / 3, kw = rem % 3;
-      int yy = o / 24, xx = o % 24;
-      imt[nr * MC2FW_LD + (o - obase)] =
-          a1b[ci * 676 + (yy + kh) * 26 + xx + kw];
-    }
+    #pragma unroll
+    for (int p = 0; p < 5; ++p)
+      #pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        int j = threadIdx.x + 128 * h;
+        if (j < C2W_PS) apl[p * C2W_PS + j] = pa[p][h];
+      }
     __syncthreads();
-    #pragma unroll 8
-    for (int k0 = 0; k0 < 288; k0 += 4) {
-      int o = k0 + kc;
-      float a = dzl[(csub * 16 + il) * MC2FW_LD + o];
-      float bv = imt[(nt * 16 + il) * MC2FW_LD + o];
-      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a, bv, acc, 0, 0, 0);
-    }
+    if (c + 1 < 24 / C2W_ROWS) fetch(c + 1);
+    #pragma unroll
+    for (int y = 0; y < C2W_ROWS; ++y)
+      #pragma unroll
+      for (int s = 0; s < 6; ++s) {
+        float a0 = dzl[aoff[0] + y * 24 + 4 * s];
+        float a1v = dzl[aoff[1] + y * 24 + 4 * s];
+        float b0 = apl[boff[0] + y * 26 + 4 * s];
+        float b1 = apl[boff[1] + y * 26 + 4 * s];
+        acc[0][0] =
+            __builtin_amdgcn_mfma_f32_16x16x4f32(a0, b0, acc[0][0], 0, 0, 0);
+        acc[0][1] =
+            __builtin_amdgcn_mfma_f32_16x16x4f32(a0, b1, acc[0][1], 0, 0, 0);
+        acc[1][0] =
+            __builtin_amdgcn_mfma_f32_16x16x4f32(a1v, b0, acc[1][0], 0, 0, 0);
+        acc[1][1] =
+            __builtin_amdgcn_mfma_f32_16x16x4f32(a1v, b1, acc[1][1], 0, 0, 0);
+      }
   }
   float* out = slab + g * 18432;
-  int orow = ch * 32 + csub * 16 + (lane >> 4) * 4;
   #pragma unroll
-  for (int r = 0; r < 4; ++r)
-    out[(orow + r) * 288 + nb * 32 + nt * 16 + il] = acc[r];
+  for (int mt = 0; mt < 2; ++mt) {
+    int orow = w * 32 + mt * 16 + kc * 4;
+    #pragma unroll
+    for (int nt = 0; nt < 2; ++nt)
+      #pragma unroll
+      for (int r = 0; r < 4; ++r)
+        out[(orow + r) * 288 + nb * 32 + nt * 16 + il] = acc[mt][nt][r];
+  }
 }
 
 __global__ void k_conv2_bwd_w_fold_mb(const float* __restrict__ slab,
@@ -771,49 +877,104 @@ __global__ void k_conv2_bwd_b_mb(const float* __restrict__ dz2,
   }
 }
 
-// conv2 backward data (f32 MFMA): 32-row materialized-im2col tiles
-// (74.9 KB LDS -> 2 blocks/CU), one accumulator per wave (wave w:
-// m-subtile w&1, ci-tile w>>1), B streamed from the per-batch global
-// w2rot layout with lane-contiguous 64 B groups.  grid = G * 22.
+// conv2 backward data (f32 MFMA), implicit GEMM from a zero-padded dz2.
+// grid = G * C2X_BLKS; a block owns 128 consecutive output positions
+// (m = p*26 + q) x all 32 ci of one image.  It stages, once and with no
+// per-element index arithmetic, the <= 8 padded dz2 rows those positions
+// read for all 64 co: each (co, row) task loads one 96 B row as float4s
+// and writes it as a 28-float row with a 2-column zero halo; rows outside
+// the image are zero rows, so the k-loop has no bounds test.  56 KB ->
+// 2 blocks/CU.  Wave w owns a 2 x 2 block of accumulators (positions
+// 32w..32w+31, both ci tiles); each W2 fragment (one global load per
+// k-step from w2rot) and each dz2 fragment feeds 2 MFMAs.  Every output's
+// k order is (co,kh,kw) ascending from 0; the a1 > 0 mask is applied at
+// the store.  Positions past 675 in the last block are clamped for the
+// reads and never stored.
+#define C2X_MT 128                      /* output positions per block */
+#define C2X_BLKS ((676 + C2X_MT - 1) / C2X_MT)
+#define C2X_ROWS 8                      /* staged padded rows per co */
+#define C2X_CS (C2X_ROWS * 28)          /* staged floats per co plane */
+static_assert((25 + C2X_MT + 25) / 26 + 2 <= C2X_ROWS,
+              "conv2 bwd_x: a block's positions span at most ROWS-2 rows");
 __global__ __launch_bounds__(256)
 void k_conv2_bwd_x_mfma_mb(const float* __restrict__ dz2,
                            const float* __restrict__ w2rot_stack,
                            const float* __restrict__ a1, int bs, int K,
                            float* __restrict__ dz1) {
-  __shared__ float imc[32 * MC2F_LD];
-  long long g = blockIdx.x / 22;
-  int mt = blockIdx.x % 22;
+  __shared__ __attribute__((aligned(16))) float lds[64 * C2X_CS];
+  long long g = blockIdx.x / C2X_BLKS;
+  int mb = blockIdx.x % C2X_BLKS;
   int k = (int)(g / bs);
+  int m0 = mb * C2X_MT, p0 = m0 / 26;
   const float* dzb = dz2 + g * 36864;
-  const float* w2rot = w2rot_stack + (long long)k * 18432;
-  for (int i = threadIdx.x; i < 32 * 576; i += 256) {
-    int mr = i / 576, kk = i % 576;
-    int m = mt * 32 + mr, p = m / 26, q = m % 26;
-    int co = kk / 9, rem = kk % 9, kh = rem / 3, kw = rem % 3;
-    int y = p - kh, x = q - kw;
-    imc[mr * MC2F_LD + kk] =
-        (m < 676 && y >= 0 && y < 24 && x >= 0 && x < 24)
-            ? dzb[co * 576 + y * 24 + x] : 0.f;
+  // staged row lr of plane co holds dz2 row p0 + lr - 2 at columns 2..25
+  for (int task = threadIdx.x; task < 64 * C2X_ROWS; task += 256) {
+    int co = task / C2X_ROWS, lr = task % C2X_ROWS;
+    int y = p0 + lr - 2;
+    float4 s[6];
+    if (y >= 0 && y < 24) {
+      const float4* sp =
+          reinterpret_cast<const float4*>(dzb + co * 576 + y * 24);
+      #pragma unroll
+      for (int u = 0; u < 6; ++u) s[u] = sp[u];
+    } else {
+      #pragma unroll
+      for (int u = 0; u < 6; ++u) s[u] = float4{0.f, 0.f, 0.f, 0.f};
+    }
+    float4* dp = reinterpret_cast<float4*>(lds + co * C2X_CS + lr * 28);
+    dp[0] = float4{0.f, 0.f, s[0].x, s[0].y};
+    #pragma unroll
+    for (int u = 1; u < 6; ++u)
+      dp[u] = float4{s[u - 1].z, s[u - 1].w, s[u].x, s[u].y};
+    dp[6] = float4{s[5].z, s[5].w, 0.f, 0.f};
   }
   __syncthreads();
   int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   int il = lane & 15, kc = lane >> 4;
-  int msub = w & 1, nt = w >> 1;
-  f32x4 acc = {0, 0, 0, 0};
-  #pragma unroll 8
-  for (int k0 = 0; k0 < 576; k0 += 4) {
-    int kk = k0 + kc;
-    float a = imc[(msub * 16 + il) * MC2F_LD + kk];
-    float bv = w2rot[(long long)kk * 32 + nt * 16 + il];
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a, bv, acc, 0, 0, 0);
-  }
-  int om = mt * 32 + msub * 16 + (lane >> 4) * 4;
-  int ci = nt * 16 + il;
+  int mw = m0 + w * 32;
+  if (mw >= 676) return;
+  int off[9], base[2];
+  conv2_tap_offsets(kc, C2X_CS, 28, -1, off);
   #pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    if (om + r >= 676) continue;
-    long long o = (g * 32 + ci) * 676 + om + r;
-    dz1[o] = a1[o] > 0.f ? acc[r] : 0.f;
+  for (int i = 0; i < 2; ++i) {
+    int m = mw + i * 16 + il;
+    m = m < 676 ? m : 675;
+    base[i] = (m / 26 - p0 + 2) * 28 + m % 26 + 2;
+  }
+  const float* wp = w2rot_stack + (long long)k * 18432 + kc * 32 + il;
+  f32x4 acc[2][2];
+  acc[0][0] = acc[0][1] = acc[1][0] = acc[1][1] = f32x4{0, 0, 0, 0};
+  for (int t = 0; t < 16; ++t) {
+    const float* lt = lds + t * 4 * C2X_CS;
+    const float* wt = wp + t * 36 * 32;
+    #pragma unroll
+    for (int j = 0; j < 9; ++j) {
+      float b0 = wt[j * 128], b1 = wt[j * 128 + 16];
+      #pragma unroll
+      for (int i = 0; i < 2; ++i) {
+        float a = lt[base[i] + off[j]];
+        acc[i][0] =
+            __builtin_amdgcn_mfma_f32_16x16x4f32(a, b0, acc[i][0], 0, 0, 0);
+        acc[i][1] =
+            __builtin_amdgcn_mfma_f32_16x16x4f32(a, b1, acc[i][1], 0, 0, 0);
+      }
+    }
+  }
+  #pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    int om = mw + i * 16 + kc * 4;  // 4 | 676: a quad is all in or all out
+    if (om >= 676) continue;
+    #pragma unroll
+    for (int n = 0; n < 2; ++n) {
+      long long o = (g * 32 + n * 16 + il) * 676 + om;
+      float4 av = *reinterpret_cast<const float4*>(a1 + o);
+      float4 v;
+      v.x = av.x > 0.f ? acc[i][n][0] : 0.f;
+      v.y = av.y > 0.f ? acc[i][n][1] : 0.f;
+      v.z = av.z > 0.f ? acc[i][n][2] : 0.f;
+      v.w = av.w > 0.f ? acc[i][n][3] : 0.f;
+      *reinterpret_cast<float4*>(dz1 + o) = v;
+    }
   }
 }
 
@@ -1307,8 +1468,8 @@ extern "C" void launch_cnn_epoch(
                          dim3(FBLK), 0, s, params, P, o.w2, K, ws.w2t,
                          ws.w2rot);
       EPOCH_CHK("k_w2_layouts_mb");
-      hipLaunchKernelGGL(k_conv2_fwd_mfma_mb, dim3(B * 9), dim3(FBLK), 0, s,
-                         ws.a1, ws.w2t, params, P, o.b2, B, K, ws.r2);
+      hipLaunchKernelGGL(k_conv2_fwd_mfma_mb, dim3(B * C2F_SLABS),
+                         dim3(FBLK), 0, s, ws.a1, ws.w2t, params, P, o.b2, B, K, ws.r2);
     }
     EPOCH_CHK("k_conv2_fwd_mfma_mb");
     hipLaunchKernelGGL(k_pool_drop_fwd, dim3((B * 9216 + FBLK - 1) / FBLK),
@@ -1361,13 +1522,8 @@ extern "C" void launch_cnn_epoch(
       hipLaunchKernelGGL(k_conv2_bwd_w_mfma_mb_bf16, dim3(18 * B), dim3(FBLK),
                          0, s, ws.dz2, ws.a1, B, K, ws.wsl);
     } else {
-      // dz2 transposed into ws.r2, which is free after pool_drop_bwd
-      hipLaunchKernelGGL(k_dz2_transpose_mb,
-                         dim3((B * 36864 + FBLK - 1) / FBLK), dim3(FBLK), 0,
-                         s, ws.dz2, B, K, ws.r2);
-      EPOCH_CHK("k_dz2_transpose_mb");
-      hipLaunchKernelGGL(k_conv2_bwd_w_mfma_mb, dim3(18 * B), dim3(FBLK), 0,
-                         s, ws.r2, ws.a1, B, K, ws.wsl);
+      hipLaunchKernelGGL(k_conv2_bwd_w_mfma_mb, dim3(9 * B), dim3(128), 0,
+                         s, ws.dz2, ws.a1, B, K, ws.wsl);
     }
     EPOCH_CHK("k_conv2_bwd_w_mfma_mb");
     hipLaunchKernelGGL(k_conv2_bwd_w_fold_mb, dim3((18432 + FBLK - 1) / FBLK),
@@ -1382,8 +1538,9 @@ extern "C" void launch_cnn_epoch(
                          reinterpret_cast<const __bf16*>(ws.w2rot), B, K,
                          ws.a1, ws.dz1);
     else
-      hipLaunchKernelGGL(k_conv2_bwd_x_mfma_mb, dim3(B * 22), dim3(FBLK),
-                         0, s, ws.dz2, ws.w2rot, ws.a1, B, K, ws.dz1);
+      hipLaunchKernelGGL(k_conv2_bwd_x_mfma_mb, dim3(B * C2X_BLKS),
+                         dim3(FBLK), 0, s, ws.dz2, ws.w2rot, ws.a1, B, K,
+                         ws.dz1);
     EPOCH_CHK("k_conv2_bwd_x_mfma_mb");
     hipLaunchKernelGGL(k_conv1_bwd_w_mb, dim3(32), dim3(1024), 0, s,
                        ws.xb, ws.dz1, grads, P, o.w1, o.b1, B, K);
@@ -1487,8 +1644,8 @@ extern "C" void launch_cnn_round_mega(
                          dim3((int)(((long long)K * 18432 + FBLK - 1) / FBLK)),
                          dim3(FBLK), 0, s, params_stack, P, o.w2, K,
                          w2t_stack, w2rot_stack);
-      hipLaunchKernelGGL(k_conv2_fwd_mfma_mb, dim3(G * 9), dim3(FBLK), 0, s,
-                         a1, w2t_stack, params_stack, P, o.b2, bs, K, r2);
+      hipLaunchKernelGGL(k_conv2_fwd_mfma_mb, dim3(G * C2F_SLABS),
+                         dim3(FBLK), 0, s, a1, w2t_stack, params_stack, P, o.b2, bs, K, r2);
     }
     hipLaunchKernelGGL(k_pool_drop_fwd_mb,
                        dim3((int)(((long long)G * 9216 + FBLK - 1) / FBLK)),
@@ -1532,11 +1689,8 @@ extern "C" void launch_cnn_round_mega(
       hipLaunchKernelGGL(k_conv2_bwd_w_mfma_mb_bf16, dim3(18 * G), dim3(FBLK),
                          0, s, dz2, a1, bs, K, slab);
     } else {
-      hipLaunchKernelGGL(k_dz2_transpose_mb,
-                         dim3((int)(((long long)G * 36864 + FBLK - 1) / FBLK)),
-                         dim3(FBLK), 0, s, dz2, bs, K, r2);  // r2 free now
-      hipLaunchKernelGGL(k_conv2_bwd_w_mfma_mb, dim3(18 * G), dim3(FBLK),
-                         0, s, r2, a1, bs, K, slab);
+      hipLaunchKernelGGL(k_conv2_bwd_w_mfma_mb, dim3(9 * G), dim3(128),
+                         0, s, dz2, a1, bs, K, slab);
     }
     int perk_fold = (18432 + FBLK - 1) / FBLK;
     hipLaunchKernelGGL(k_conv2_bwd_w_fold_mb, dim3(K * perk_fold),
@@ -1549,8 +1703,8 @@ extern "C" void launch_cnn_round_mega(
                          reinterpret_cast<const __bf16*>(w2rot_stack),
                          bs, K, a1, dz1);
     else
-      hipLaunchKernelGGL(k_conv2_bwd_x_mfma_mb, dim3(G * 22), dim3(FBLK),
-                         0, s, dz2, w2rot_stack, a1, bs, K, dz1);
+      hipLaunchKernelGGL(k_conv2_bwd_x_mfma_mb, dim3(G * C2X_BLKS),
+                         dim3(FBLK), 0, s, dz2, w2rot_stack, a1, bs, K, dz1);
     hipLaunchKernelGGL(k_conv1_bwd_w_mb, dim3(K * 32), dim3(1024), 0, s,
                        xb, dz1, grads_stack, P, o.w1, o.b1, bs, K);
     hipMemsetAsync(acc2k, 0, 2 * K * sizeof(double), s);
@@ -1626,14 +1780,14 @@ void launch_w2_layouts(const float* w2, int K, float* w2t, float* w2rot,
 }
 void launch_conv2_fwd_mfma(const float* a1, const float* w2t, const float* b2,
                            int bs, int K, float* r2, hipStream_t s) {
-  hipLaunchKernelGGL(k_conv2_fwd_mfma_mb, dim3(K * bs * 9), dim3(FBLK), 0, s,
-                     a1, w2t, b2, 64LL, 0LL, bs, K, r2);
+  hipLaunchKernelGGL(k_conv2_fwd_mfma_mb, dim3(K * bs * C2F_SLABS),
+                     dim3(FBLK), 0, s, a1, w2t, b2, 64LL, 0LL, bs, K, r2);
 }
 void launch_conv2_bwd_x_mfma(const float* dz2, const float* w2rot,
                              const float* a1, int bs, int K, float* dz1,
                              hipStream_t s) {
-  hipLaunchKernelGGL(k_conv2_bwd_x_mfma_mb, dim3(K * bs * 22), dim3(FBLK), 0,
-                     s, dz2, w2rot, a1, bs, K, dz1);
+  hipLaunchKernelGGL(k_conv2_bwd_x_mfma_mb, dim3(K * bs * C2X_BLKS),
+                     dim3(FBLK), 0, s, dz2, w2rot, a1, bs, K, dz1);
 }
 static void conv2_bwd_w_tail(const float* dz2, const float* slab, int bs,
                              int K, float* dw2, float* db2, hipStream_t s) {
@@ -1644,13 +1798,10 @@ static void conv2_bwd_w_tail(const float* dz2, const float* slab, int bs,
                      dz2, db2, 64LL, 0LL, bs, K);
 }
 void launch_conv2_bwd_w_mfma(const float* dz2, const float* a1, int bs, int K,
-                             float* dz2t, float* slab, float* dw2, float* db2,
+                             float* slab, float* dw2, float* db2,
                              hipStream_t s) {
-  hipLaunchKernelGGL(k_dz2_transpose_mb,
-                     dim3((K * bs * 36864 + FBLK - 1) / FBLK), dim3(FBLK), 0,
-                     s, dz2, bs, K, dz2t);
-  hipLaunchKernelGGL(k_conv2_bwd_w_mfma_mb, dim3(18 * K * bs), dim3(FBLK), 0,
-                     s, dz2t, a1, bs, K, slab);
+  hipLaunchKernelGGL(k_conv2_bwd_w_mfma_mb, dim3(9 * K * bs), dim3(128), 0,
+                     s, dz2, a1, bs, K, slab);
   conv2_bwd_w_tail(dz2, slab, bs, K, dw2, db2, s);
 }
 // the seed arrives by value, so the fold runs the per-client wrapper once

@@ -26,6 +26,11 @@ inline CnnOffsets cnn_offsets(int C) {
   return o;
 }
 
+// Output rows per block of the f32 conv2 forward kernel: slab s of an
+// image covers output rows [s*ROWS, (s+1)*ROWS), so rows ROWS, 2*ROWS, ..
+// are the seams between blocks.  Exported as _C.CONV2_FWD_SLAB_ROWS.
+#define CONV2_FWD_SLAB_ROWS 4
+
 // per-client CNN workspace, laid out inside one float buffer by the
 // binding (sizes for B rows)
 struct CnnWorkspace {
@@ -154,8 +159,8 @@ void launch_conv2_bwd_x_mfma(const float* dz2, const float* w2rot,
                              const float* a1, int bs, int K, float* dz1,
                              hipStream_t s);
 void launch_conv2_bwd_w_mfma(const float* dz2, const float* a1, int bs,
-                             int K, float* dz2t, float* slab, float* dw2,
-                             float* db2, hipStream_t s);
+                             int K, float* slab, float* dw2, float* db2,
+                             hipStream_t s);
 void launch_fc1_fwd_mfma(const float* a2, const float* w3, const float* b3,
                          int bs, int K, float p2, unsigned long long seed,
                          unsigned long long offset, float* slab, float* z3,

@@ -125,7 +125,7 @@ class FusedCNNEpoch:
 class MegaRound:
     """Cross-client mega-batched round driver (csrc/fused_cnn.hip):
     ONE _C.cnn_round_mega call trains ALL K sampled clients with one
-    launch set per batch-step — grids scale by K (conv2 fwd: K*bs*9
+    launch set per batch-step — grids scale by K (conv2 fwd: K*bs*6
     blocks fills the 256-CU chip) and the host enqueues ~22 kernels per
     step instead of ~22 per client per step.  fp32 path; per-client
     dropout Philox streams are bit-identical to the per-client fused
