@@ -111,6 +111,13 @@ class ClientExecutor:
         # resident client model replica + arena
         self.model = make_model(self.model_config)
         self.arena = ParameterArena(self.model, bind_grads=True)
+        if self.client_config.get("mixed_precision", "") == "bf16":
+            # client training streams the LSTM recurrent weights as bf16
+            # (fp32 masters and arithmetic; evaluation stays fp32)
+            from ..ops.lstm import FusedLSTM
+            for m in self.model.modules():
+                if isinstance(m, FusedLSTM):
+                    m.bf16_recurrent = True
         # reusable fused optimizer (reset per client)
         opt_cfg = dict(self.client_config["optimizer_config"])
         opt_cfg.setdefault("lr", self.server_config.get("initial_lr_client", 1.0))
@@ -595,7 +602,8 @@ class ClientPool:
         if not _fused_round_eligible(prim, data_cfg):
             return None
         out = self._try_graphed_mega("_mega_lstm", True, _build_mega_lstm,
-                                     data_cfg, client_ids, initial_lr, seeds)
+                                     data_cfg, client_ids, initial_lr, seeds,
+                                     precisions=("bf16",))
         if out is None:
             # OPT-IN: measured SLOWER than the per-client epoch-graph path
             # on ROCm 7.2 — MIOpen decomposes groups=K convs into K
@@ -662,19 +670,23 @@ class ClientPool:
         return outputs
 
     def _try_graphed_mega(self, attr, enabled, build, data_cfg, client_ids,
-                          initial_lr, seeds):
+                          initial_lr, seeds, precisions=()):
         """One graph-captured cross-client round
         (ops/mega_round.GraphedMegaRound) when the model being trained is
         the one ``build(prim, data_cfg)`` recognises (it returns the
         driver, or None for any other model); the driver is kept in
-        ``self.<attr>``.  Returns outputs or None if not this task /
-        ineligible."""
+        ``self.<attr>``.  ``precisions`` lists the ``mixed_precision``
+        values the driver implements besides fp32.  Returns outputs or
+        None if not this task / ineligible."""
         prim = self.executors[0]
         cc = prim.client_config
         if getattr(self, attr) is False or not enabled:
             return None
-        if not cc.get("use_mega_round", True) or cc.get("mixed_precision"):
-            return None  # the graphed rounds are fp32
+        if not cc.get("use_mega_round", True):
+            return None
+        mp = cc.get("mixed_precision")
+        if mp and mp not in precisions:
+            return None  # the graphed rounds are fp32 unless they say so
         if prim.arena is None or prim.arena.device.type != "cuda":
             return None
         opt_cfg = cc.get("optimizer_config", {})
@@ -712,8 +724,10 @@ def _build_mega_lstm(prim, data_cfg):
     from ..ops.mega_shakespeare import ShakespeareMegaRound, matches_char_lstm
     if matches_char_lstm(prim.arena) is None:
         return None
-    return ShakespeareMegaRound(prim.arena, data_cfg.get("batch_size", 4),
-                                data_cfg.get("max_grad_norm"))
+    return ShakespeareMegaRound(
+        prim.arena, data_cfg.get("batch_size", 4),
+        data_cfg.get("max_grad_norm"),
+        use_bf16=prim.client_config.get("mixed_precision", "") == "bf16")
 
 
 def _build_mega_resnet(prim, data_cfg):

@@ -326,11 +326,30 @@ void cnn_round(torch::Tensor shard_x, torch::Tensor shard_y,
 // launch over xp [R, T, 4H] and K-stacked float4-packed hidden weights
 // (ops/lstm._pack_fwd / _pack_bwd); row r belongs to client
 // r / rows_per_client.  Forward returns (h_seq, activated gates, cell
-// states).
+// states).  Both dispatch on w_packed_stack's dtype: float32 as above,
+// bfloat16 = the bf16-stored layouts of ops/lstm._pack_fwd_bf16 /
+// _pack_bwd_bf16 (same element count; everything else stays fp32).
+static bool lstm_w_is_bf16(const torch::Tensor& w, const char* layout) {
+  if (w.scalar_type() == torch::kFloat32) {
+    check_flat(w, "w_packed_stack");
+    return false;
+  }
+  TORCH_CHECK(w.scalar_type() == torch::kBFloat16,
+              "w_packed_stack must be float32 or bfloat16");
+  TORCH_CHECK(w.is_cuda(), "w_packed_stack must be a GPU tensor");
+  TORCH_CHECK(w.is_contiguous(), "w_packed_stack must be contiguous ",
+              layout);
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(w.data_ptr()) % 16 == 0,
+              "w_packed_stack must be 16-byte aligned");
+  return true;
+}
+
 std::vector<torch::Tensor> lstm_seq_fwd(torch::Tensor xp,
                                         torch::Tensor w_packed_stack,
                                         int64_t rows_per_client) {
-  check_flat(xp, "xp"); check_flat(w_packed_stack, "w_packed_stack");
+  check_flat(xp, "xp");
+  bool bf16 = lstm_w_is_bf16(w_packed_stack,
+                             "[K, 256/8, 4*256, 8] (ops/lstm._pack_fwd_bf16)");
   TORCH_CHECK(xp.dim() == 3 && xp.size(2) == 4 * 256,
               "fused LSTM supports hidden size 256: xp must be "
               "[R, T, 4*256]");
@@ -343,11 +362,19 @@ std::vector<torch::Tensor> lstm_seq_fwd(torch::Tensor xp,
   auto h_seq = torch::empty({R, T, 256}, xp.options());
   auto gates = torch::empty({R, T, 4 * 256}, xp.options());
   auto c_seq = torch::empty({R, T, 256}, xp.options());
-  launch_lstm_seq_fwd(xp.data_ptr<float>(),
-                      w_packed_stack.data_ptr<float>(),
-                      h_seq.data_ptr<float>(), gates.data_ptr<float>(),
-                      c_seq.data_ptr<float>(), (int)R,
-                      (int)rows_per_client, (int)T, cur_stream());
+  if (bf16)
+    launch_lstm_seq_fwd_bf16(
+        xp.data_ptr<float>(),
+        static_cast<const unsigned short*>(w_packed_stack.data_ptr()),
+        h_seq.data_ptr<float>(), gates.data_ptr<float>(),
+        c_seq.data_ptr<float>(), (int)R, (int)rows_per_client, (int)T,
+        cur_stream());
+  else
+    launch_lstm_seq_fwd(xp.data_ptr<float>(),
+                        w_packed_stack.data_ptr<float>(),
+                        h_seq.data_ptr<float>(), gates.data_ptr<float>(),
+                        c_seq.data_ptr<float>(), (int)R,
+                        (int)rows_per_client, (int)T, cur_stream());
   return {h_seq, gates, c_seq};
 }
 
@@ -355,7 +382,8 @@ torch::Tensor lstm_seq_bwd(torch::Tensor gates, torch::Tensor c_seq,
                            torch::Tensor w_packed_stack,
                            torch::Tensor dh_out, int64_t rows_per_client) {
   check_flat(gates, "gates"); check_flat(c_seq, "c_seq");
-  check_flat(w_packed_stack, "w_packed_stack");
+  bool bf16 = lstm_w_is_bf16(w_packed_stack,
+                             "[K, 4*256/8, 256, 8] (ops/lstm._pack_bwd_bf16)");
   check_flat(dh_out, "dh_out");
   long long R = gates.size(0), T = gates.size(1);
   TORCH_CHECK(rows_per_client > 0 && R % rows_per_client == 0);
@@ -364,10 +392,17 @@ torch::Tensor lstm_seq_bwd(torch::Tensor gates, torch::Tensor c_seq,
               "w_packed_stack must be [K, 4*256/4, 256, 4] "
               "(ops/lstm._pack_bwd)");
   auto dg = torch::empty_like(gates);
-  launch_lstm_seq_bwd(gates.data_ptr<float>(), c_seq.data_ptr<float>(),
-                      w_packed_stack.data_ptr<float>(),
-                      dh_out.data_ptr<float>(), dg.data_ptr<float>(),
-                      (int)R, (int)rows_per_client, (int)T, cur_stream());
+  if (bf16)
+    launch_lstm_seq_bwd_bf16(
+        gates.data_ptr<float>(), c_seq.data_ptr<float>(),
+        static_cast<const unsigned short*>(w_packed_stack.data_ptr()),
+        dh_out.data_ptr<float>(), dg.data_ptr<float>(), (int)R,
+        (int)rows_per_client, (int)T, cur_stream());
+  else
+    launch_lstm_seq_bwd(gates.data_ptr<float>(), c_seq.data_ptr<float>(),
+                        w_packed_stack.data_ptr<float>(),
+                        dh_out.data_ptr<float>(), dg.data_ptr<float>(),
+                        (int)R, (int)rows_per_client, (int)T, cur_stream());
   return dg;
 }
 

@@ -93,6 +93,17 @@ void launch_lstm_seq_bwd(const float* gates, const float* c_seq,
                          const float* w_hh_stack, const float* dh_out,
                          float* dg_pre, int R, int rows_per_client, int T,
                          hipStream_t s);
+// the same kernels on bf16-stored W_hh (8 k's per 16-byte group,
+// ops/lstm._pack_fwd_bf16 / _pack_bwd_bf16); all arithmetic stays fp32
+void launch_lstm_seq_fwd_bf16(const float* xp,
+                              const unsigned short* w_hh_t_stack,
+                              float* h_seq, float* gates, float* c_seq,
+                              int R, int rows_per_client, int T,
+                              hipStream_t s);
+void launch_lstm_seq_bwd_bf16(const float* gates, const float* c_seq,
+                              const unsigned short* w_hh_stack,
+                              const float* dh_out, float* dg_pre, int R,
+                              int rows_per_client, int T, hipStream_t s);
 
 // gru_seq.hip
 void launch_gru_seq_fwd(const float* gi, const float* whh_t,

@@ -25,6 +25,14 @@
 // float4-packed W_hh (ops/lstm._pack_fwd / _pack_bwd).  One launch covers
 // a whole cohort's recurrence (Shakespeare mega round); the per-client
 // FusedLSTM is the same launch at K = 1, rows_per_client = B.
+//
+// Each kernel is ONE templated body instantiated for two weight storage
+// formats (WF32 / WBF16 below).  bf16 is a STORAGE format only: a packed
+// word widens to two exact fp32 values in the k-loop (u << 16,
+// u & 0xffff0000) and every product and sum stays fp32, so the bf16
+// instantiation computes the fp32 kernel on bf16-rounded W_hh — k by k
+// in the same four accumulator chains, so bit for bit.  Half the bytes
+// per k halves the per-step L2 stream that bounds the fp32 kernels.
 
 #include <hip/hip_runtime.h>
 
@@ -34,19 +42,103 @@
 // float4 weight groups each thread keeps in registers across all T steps
 // (16 is the 128-VGPR/16-wave occupancy limit, 24 spills)
 #define LSTM_WREG 16
+// The same for the bf16 kernels' 8-k groups, with the unroll of the
+// streamed loop (loads issued back to back).  With half the bytes per k
+// the stream no longer bounds the kernel and the widening costs one VALU
+// op per k wherever the word lives, so MORE resident groups do not help:
+// measured at K = 10 x 4 rows, T = 80 (profiles/r04_shakespeare_bf16_stats.md),
+// forward 4 resident + 28 streamed in one batch beat 16 + 16 by 10 %, and
+// backward 8 + 24 (unroll 16) beat 16 + 16 (unroll 8) by 13 %.  Both
+// compile to zero scratch at 4 waves/SIMD; the table there lists the
+// combinations that spill.  -D overrides reproduce that table.
+#ifndef LSTM_WREG_BF16_FWD
+#define LSTM_WREG_BF16_FWD 4
+#endif
+#ifndef LSTM_UNROLL_BF16_FWD
+#define LSTM_UNROLL_BF16_FWD 28
+#endif
+#ifndef LSTM_WREG_BF16_BWD
+#define LSTM_WREG_BF16_BWD 8
+#endif
+#ifndef LSTM_UNROLL_BF16_BWD
+#define LSTM_UNROLL_BF16_BWD 16
+#endif
 
 __device__ inline float sigf(float x) { return 1.f / (1.f + __expf(-x)); }
 
+// Weight storage formats.  A GROUP is one 16-byte load: KPG consecutive
+// k's of one column.  fma() adds group kk's products with the fp32
+// vector v (h_prev or dg, read from LDS as float4) into four independent
+// accumulator chains; pin() is called on a register-resident group at
+// its use inside the t loop.
+struct WF32 {
+  using elem = float;
+  using vec = float4;
+  static constexpr int KPG = 4;
+  static constexpr int REG_FWD = LSTM_WREG, REG_BWD = LSTM_WREG;
+  // loads of the streamed loop issued back to back
+  static constexpr int UNROLL_FWD = 16, UNROLL_BWD = 16;
+  static __device__ inline void pin(vec&) {}
+  static __device__ inline void fma(const vec& w, const float4* v, int kk,
+                                    float& s0, float& s1, float& s2,
+                                    float& s3) {
+    float4 hv = v[kk];
+    s0 = fmaf(w.x, hv.x, s0);
+    s1 = fmaf(w.y, hv.y, s1);
+    s2 = fmaf(w.z, hv.z, s2);
+    s3 = fmaf(w.w, hv.w, s3);
+  }
+};
+
+struct WBF16 {
+  using elem = unsigned short; // raw bf16 bits
+  using vec = uint4;           // 8 of them; element d even = low half of word
+  static constexpr int KPG = 8;
+  static constexpr int REG_FWD = LSTM_WREG_BF16_FWD;
+  static constexpr int REG_BWD = LSTM_WREG_BF16_BWD;
+  static constexpr int UNROLL_FWD = LSTM_UNROLL_BF16_FWD;
+  static constexpr int UNROLL_BWD = LSTM_UNROLL_BF16_BWD;
+  static __device__ inline float lo(unsigned u) {
+    return __uint_as_float(u << 16);
+  }
+  static __device__ inline float hi(unsigned u) {
+    return __uint_as_float(u & 0xffff0000u);
+  }
+  // The packed words are loop-invariant, so the compiler hoists their
+  // widening out of the t loop and keeps the fp32 values instead: 8
+  // VGPRs per group where 4 were planned (11 resident groups spill).
+  // An empty statement that claims to rewrite the words pins the
+  // widening to where the group is used.
+  static __device__ inline void pin(vec& w) {
+    asm volatile("" : "+v"(w.x), "+v"(w.y), "+v"(w.z), "+v"(w.w));
+  }
+  static __device__ inline void fma(const vec& w, const float4* v, int kk,
+                                    float& s0, float& s1, float& s2,
+                                    float& s3) {
+    float4 ha = v[2 * kk], hb = v[2 * kk + 1];
+    s0 = fmaf(lo(w.x), ha.x, s0);
+    s1 = fmaf(hi(w.x), ha.y, s1);
+    s2 = fmaf(lo(w.y), ha.z, s2);
+    s3 = fmaf(hi(w.y), ha.w, s3);
+    s0 = fmaf(lo(w.z), hb.x, s0);
+    s1 = fmaf(hi(w.z), hb.y, s1);
+    s2 = fmaf(lo(w.w), hb.z, s2);
+    s3 = fmaf(hi(w.w), hb.w, s3);
+  }
+};
+
 // xp:           [R, T, 4H]  pre-activation input projection (order ifgo)
-// w_hh_t_stack: [K, H/4, 4H, 4]  packed transposed W_hh per client
+// w_hh_t_stack: [K, H/KPG, 4H, KPG]  packed transposed W_hh per client
+//               (fp32: ops/lstm._pack_fwd, bf16: _pack_fwd_bf16)
 // h_seq:        [R, T, H]   out
 // gates:        [R, T, 4H]  out (ACTIVATED i,f,g,o — saved for backward)
 // c_seq:        [R, T, H]   out (cell states)
 // thread = gate column j = g*H + h, so the per-step GEMV reads its weight
 // column fully coalesced.
+template <typename W>
 __global__ __launch_bounds__(1024)
 void k_lstm_seq_fwd(const float* __restrict__ xp,
-                    const float* __restrict__ w_hh_t_stack,
+                    const typename W::elem* __restrict__ w_hh_t_stack,
                     float* __restrict__ h_seq,
                     float* __restrict__ gates,
                     float* __restrict__ c_seq, int rows_per_client,
@@ -56,18 +148,20 @@ void k_lstm_seq_fwd(const float* __restrict__ xp,
   int tid = threadIdx.x;
   int g = tid >> 8;
   int b = blockIdx.x;
-  const float* w_hh_t = w_hh_t_stack
+  using wvec = typename W::vec;
+  constexpr int NG = LSTM_H / W::KPG;     // weight groups per column
+  const typename W::elem* w_hh_t = w_hh_t_stack
       + (long long)(b / rows_per_client) * LSTM_H * 4 * LSTM_H;
-  const float4* wp = reinterpret_cast<const float4*>(w_hh_t);
+  const wvec* wp = reinterpret_cast<const wvec*>(w_hh_t);
   const float4* hp4 = reinterpret_cast<const float4*>(h_prev);
   if (tid < LSTM_H) h_prev[tid] = 0.f;
   float c = 0.f;
-  // weights are time-invariant: keep the first LSTM_WREG float4 groups of
-  // this thread's column resident in registers across ALL T steps
-  // (removes 1/4 of the latency-bound per-step loads)
-  float4 wreg[LSTM_WREG];
+  // weights are time-invariant: keep the first REG_FWD groups of this
+  // thread's column resident in registers across ALL T steps (fp32: 64
+  // k's, removes 1/4 of the latency-bound per-step loads; bf16: 32 k's)
+  wvec wreg[W::REG_FWD];
   #pragma unroll
-  for (int kk = 0; kk < LSTM_WREG; ++kk)
+  for (int kk = 0; kk < W::REG_FWD; ++kk)
     wreg[kk] = wp[(long long)kk * 4 * LSTM_H + tid];
   __syncthreads();
   for (int t = 0; t < T; ++t) {
@@ -77,21 +171,14 @@ void k_lstm_seq_fwd(const float* __restrict__ xp,
     // exposed L2 latency x load count (256 loads/step/thread -> 64)
     float s0 = xr[tid], s1 = 0.f, s2 = 0.f, s3 = 0.f;
     #pragma unroll
-    for (int kk = 0; kk < LSTM_WREG; ++kk) {
-      float4 hv = hp4[kk];
-      s0 = fmaf(wreg[kk].x, hv.x, s0);
-      s1 = fmaf(wreg[kk].y, hv.y, s1);
-      s2 = fmaf(wreg[kk].z, hv.z, s2);
-      s3 = fmaf(wreg[kk].w, hv.w, s3);
+    for (int kk = 0; kk < W::REG_FWD; ++kk) {
+      W::pin(wreg[kk]);
+      W::fma(wreg[kk], hp4, kk, s0, s1, s2, s3);
     }
-    #pragma unroll 16
-    for (int kk = LSTM_WREG; kk < LSTM_H / 4; ++kk) {
-      float4 wv = wp[(long long)kk * 4 * LSTM_H + tid];
-      float4 hv = hp4[kk];
-      s0 = fmaf(wv.x, hv.x, s0);
-      s1 = fmaf(wv.y, hv.y, s1);
-      s2 = fmaf(wv.z, hv.z, s2);
-      s3 = fmaf(wv.w, hv.w, s3);
+    #pragma unroll W::UNROLL_FWD
+    for (int kk = W::REG_FWD; kk < NG; ++kk) {
+      wvec wv = wp[(long long)kk * 4 * LSTM_H + tid];
+      W::fma(wv, hp4, kk, s0, s1, s2, s3);
     }
     float s = (s0 + s1) + (s2 + s3);
     float act = (g == 2) ? tanhf(s) : sigf(s);
@@ -114,12 +201,14 @@ void k_lstm_seq_fwd(const float* __restrict__ xp,
 
 // Backward: dh_out [R, T, H] upstream grads of h_seq; produces
 // dg_pre [R, T, 4H] (pre-activation gate grads == grads of xp).
-// w_hh_stack: [K, 4H/4, H, 4] packed W_hh per client; thread (q, h) sums
-// its 256-row quarter of W_hh^T dg with lane-coalesced reads.
+// w_hh_stack: [K, 4H/KPG, H, KPG] packed W_hh per client (fp32:
+// ops/lstm._pack_bwd, bf16: _pack_bwd_bf16); thread (q, h) sums its
+// 256-row quarter of W_hh^T dg with lane-coalesced reads.
+template <typename W>
 __global__ __launch_bounds__(1024)
 void k_lstm_seq_bwd(const float* __restrict__ gates,
                     const float* __restrict__ c_seq,
-                    const float* __restrict__ w_hh_stack,
+                    const typename W::elem* __restrict__ w_hh_stack,
                     const float* __restrict__ dh_out,
                     float* __restrict__ dg_pre, int rows_per_client,
                     int T) {
@@ -129,18 +218,20 @@ void k_lstm_seq_bwd(const float* __restrict__ gates,
   int tid = threadIdx.x;
   int h = tid & (LSTM_H - 1), q = tid >> 8;
   int b = blockIdx.x;
-  const float* w_hh = w_hh_stack
+  using wvec = typename W::vec;
+  constexpr int NG = LSTM_H / W::KPG;     // weight groups per quarter
+  const typename W::elem* w_hh = w_hh_stack
       + (long long)(b / rows_per_client) * 4 * LSTM_H * LSTM_H;
-  const float4* wpB = reinterpret_cast<const float4*>(w_hh);
+  const wvec* wpB = reinterpret_cast<const wvec*>(w_hh) + h;
   const float4* dgp4 = reinterpret_cast<const float4*>(dg_l);
   float dc = 0.f;
   if (tid < LSTM_H) dh_rec_l[tid] = 0.f;
-  // register-resident first LSTM_WREG weight groups of this thread's
+  // register-resident first REG_BWD weight groups of this thread's
   // quarter (time-invariant across the BPTT loop)
-  float4 wregB[LSTM_WREG];
+  wvec wregB[W::REG_BWD];
   #pragma unroll
-  for (int jj = 0; jj < LSTM_WREG; ++jj)
-    wregB[jj] = wpB[(long long)(q * (LSTM_H / 4) + jj) * LSTM_H + h];
+  for (int jj = 0; jj < W::REG_BWD; ++jj)
+    wregB[jj] = wpB[(long long)(q * NG + jj) * LSTM_H];
   __syncthreads();
   for (int t = T - 1; t >= 0; --t) {
     long long base = ((long long)b * T + t) * 4 * LSTM_H;
@@ -172,22 +263,15 @@ void k_lstm_seq_bwd(const float* __restrict__ gates,
     __syncthreads();
     float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
     #pragma unroll
-    for (int jj = 0; jj < LSTM_WREG; ++jj) {
-      float4 dv = dgp4[q * (LSTM_H / 4) + jj];
-      s0 = fmaf(wregB[jj].x, dv.x, s0);
-      s1 = fmaf(wregB[jj].y, dv.y, s1);
-      s2 = fmaf(wregB[jj].z, dv.z, s2);
-      s3 = fmaf(wregB[jj].w, dv.w, s3);
+    for (int jj = 0; jj < W::REG_BWD; ++jj) {
+      W::pin(wregB[jj]);
+      W::fma(wregB[jj], dgp4, q * NG + jj, s0, s1, s2, s3);
     }
-    #pragma unroll 16
-    for (int jj = LSTM_WREG; jj < LSTM_H / 4; ++jj) {
-      int jg = q * (LSTM_H / 4) + jj;    // float4 group of 4 j's
-      float4 wv = wpB[(long long)jg * LSTM_H + h];
-      float4 dv = dgp4[jg];
-      s0 = fmaf(wv.x, dv.x, s0);
-      s1 = fmaf(wv.y, dv.y, s1);
-      s2 = fmaf(wv.z, dv.z, s2);
-      s3 = fmaf(wv.w, dv.w, s3);
+    #pragma unroll W::UNROLL_BWD
+    for (int jj = W::REG_BWD; jj < NG; ++jj) {
+      int jg = q * NG + jj;              // group of KPG j's
+      wvec wv = wpB[(long long)jg * LSTM_H];
+      W::fma(wv, dgp4, jg, s0, s1, s2, s3);
     }
     float s = (s0 + s1) + (s2 + s3);
     part[tid] = s;
@@ -204,7 +288,7 @@ extern "C" {
 void launch_lstm_seq_fwd(const float* xp, const float* w_hh_t_stack,
                          float* h_seq, float* gates, float* c_seq, int R,
                          int rows_per_client, int T, hipStream_t s) {
-  hipLaunchKernelGGL(k_lstm_seq_fwd, dim3(R), dim3(4 * LSTM_H), 0, s,
+  hipLaunchKernelGGL(k_lstm_seq_fwd<WF32>, dim3(R), dim3(4 * LSTM_H), 0, s,
                      xp, w_hh_t_stack, h_seq, gates, c_seq,
                      rows_per_client, T);
 }
@@ -213,7 +297,27 @@ void launch_lstm_seq_bwd(const float* gates, const float* c_seq,
                          const float* w_hh_stack, const float* dh_out,
                          float* dg_pre, int R, int rows_per_client, int T,
                          hipStream_t s) {
-  hipLaunchKernelGGL(k_lstm_seq_bwd, dim3(R), dim3(4 * LSTM_H), 0, s,
+  hipLaunchKernelGGL(k_lstm_seq_bwd<WF32>, dim3(R), dim3(4 * LSTM_H), 0, s,
+                     gates, c_seq, w_hh_stack, dh_out, dg_pre,
+                     rows_per_client, T);
+}
+
+// bf16-stored weights (raw 16-bit words; 16-byte aligned stacks)
+void launch_lstm_seq_fwd_bf16(const float* xp,
+                              const unsigned short* w_hh_t_stack,
+                              float* h_seq, float* gates, float* c_seq,
+                              int R, int rows_per_client, int T,
+                              hipStream_t s) {
+  hipLaunchKernelGGL(k_lstm_seq_fwd<WBF16>, dim3(R), dim3(4 * LSTM_H), 0, s,
+                     xp, w_hh_t_stack, h_seq, gates, c_seq,
+                     rows_per_client, T);
+}
+
+void launch_lstm_seq_bwd_bf16(const float* gates, const float* c_seq,
+                              const unsigned short* w_hh_stack,
+                              const float* dh_out, float* dg_pre, int R,
+                              int rows_per_client, int T, hipStream_t s) {
+  hipLaunchKernelGGL(k_lstm_seq_bwd<WBF16>, dim3(R), dim3(4 * LSTM_H), 0, s,
                      gates, c_seq, w_hh_stack, dh_out, dg_pre,
                      rows_per_client, T);
 }

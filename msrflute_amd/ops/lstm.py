@@ -37,24 +37,55 @@ def _pack_bwd(w_hh):
     return w_hh.reshape(*lead, H4 // 4, 4, H).transpose(-1, -2).contiguous()
 
 
+def _to_bf16(view):
+    """Contiguous bf16 copy of a strided fp32 view: one kernel that
+    permutes and rounds (to nearest even)."""
+    return torch.empty(view.shape, dtype=torch.bfloat16,
+                       device=view.device).copy_(view)
+
+
+def _pack_fwd_bf16(w_hh):
+    """[..., 4H, H] -> bf16 [..., H/8, 4H, 8]: element (kk, j, d) =
+    bf16(W_hh[j, 8kk+d]) — one 16-byte load per 8 hidden units; element
+    d even is the low half of its 32-bit word.  Leading dims pass through."""
+    *lead, H4, H = w_hh.shape
+    return _to_bf16(w_hh.transpose(-1, -2).reshape(*lead, H // 8, 8, H4)
+                    .transpose(-1, -2))
+
+
+def _pack_bwd_bf16(w_hh):
+    """[..., 4H, H] -> bf16 [..., 4H/8, H, 8]: element (jg, h, d) =
+    bf16(W_hh[8jg+d, h])."""
+    *lead, H4, H = w_hh.shape
+    return _to_bf16(w_hh.reshape(*lead, H4 // 8, 8, H).transpose(-1, -2))
+
+
 class _LSTMSeq(torch.autograd.Function):
     """One LSTM layer's recurrence over xp [R, T, 4H] with K-stacked
     hidden weights w_hh_stack [K, 4H, H]: row r uses client
-    r // rows_per_client's weights (K = 1: one model, rows_per_client = R)."""
+    r // rows_per_client's weights (K = 1: one model, rows_per_client = R).
+
+    ``bf16_weights``: both kernels read W_hh rounded to bf16 (packed anew
+    on every call — SGD moves the fp32 masters every step) and compute in
+    fp32, i.e. this layer evaluated at ``w.bfloat16().float()``; dW_hh is
+    the same fp32 GEMM and lands on the master (straight-through)."""
 
     @staticmethod
-    def forward(ctx, xp, w_hh_stack, rows_per_client):
+    def forward(ctx, xp, w_hh_stack, rows_per_client, bf16_weights=False):
+        pack = _pack_fwd_bf16 if bf16_weights else _pack_fwd
         h_seq, gates, c_seq = _C.lstm_seq_fwd(
-            xp.contiguous(), _pack_fwd(w_hh_stack), rows_per_client)
+            xp.contiguous(), pack(w_hh_stack), rows_per_client)
         ctx.save_for_backward(gates, c_seq, w_hh_stack, h_seq)
         ctx.rows_per_client = rows_per_client
+        ctx.bf16_weights = bf16_weights
         return h_seq
 
     @staticmethod
     def backward(ctx, dh):
         gates, c_seq, w_hh_stack, h_seq = ctx.saved_tensors
         rpc = ctx.rows_per_client
-        dg = _C.lstm_seq_bwd(gates, c_seq, _pack_bwd(w_hh_stack),
+        pack = _pack_bwd_bf16 if ctx.bf16_weights else _pack_bwd
+        dg = _C.lstm_seq_bwd(gates, c_seq, pack(w_hh_stack),
                              dh.contiguous(), rpc)
         R, T, H = h_seq.shape
         K = R // rpc
@@ -63,12 +94,21 @@ class _LSTMSeq(torch.autograd.Function):
         # batched GEMM over the stacked steps
         dw_hh = torch.bmm(dg.view(K, rpc * T, 4 * H).transpose(1, 2),
                           h_prev.view(K, rpc * T, H))
-        return dg, dw_hh, None
+        # one None per non-tensor argument; autograd drops the last when
+        # apply() was called without bf16_weights
+        return dg, dw_hh, None, None
 
 
 class FusedLSTM(nn.Module):
     """Unidirectional batch-first LSTM; inter-layer dropout unsupported
-    (the benchmark models use dropout=0)."""
+    (the benchmark models use dropout=0).
+
+    ``bf16_recurrent`` (off by default; ``client_config.mixed_precision:
+    bf16`` sets it on client models) makes TRAINING-mode calls of the
+    fused path stream W_hh as bf16 (see ``_LSTMSeq``).  Evaluation stays
+    fp32, so metrics are a function of the master weights alone."""
+
+    bf16_recurrent = False
 
     def __init__(self, input_size, hidden_size, num_layers=1,
                  batch_first=True):
@@ -94,12 +134,13 @@ class FusedLSTM(nn.Module):
             self._fallback.flatten_parameters = lambda: None  # shared params
             return self._fallback(x, hx)
         h = x
+        bf16 = bool(self.bf16_recurrent and self.training)
         for k in range(self.num_layers):
             w_ih = getattr(self, f"weight_ih_l{k}")
             w_hh = getattr(self, f"weight_hh_l{k}")
             b = getattr(self, f"bias_ih_l{k}") + getattr(self, f"bias_hh_l{k}")
             xp = h.matmul(w_ih.t()) + b
-            h = _LSTMSeq.apply(xp, w_hh.unsqueeze(0), x.shape[0])
+            h = _LSTMSeq.apply(xp, w_hh.unsqueeze(0), x.shape[0], bf16)
         return h, None
 
 

@@ -25,6 +25,10 @@ ALL K sampled clients train together with K-stacked per-client weights:
   (ignore_index 0), so their CE contributions AND gradients are exactly
   zero — finished clients' SGD no-ops (the CNN mega round's trick).
 
+``use_bf16`` (``client_config.mixed_precision: bf16``) switches both
+recurrences to bf16-stored W_hh, as the per-client FusedLSTM does under
+the same flag.
+
 Per-client numerics match the per-client FusedLSTM path: same recurrence
 kernel math, same per-batch mean-CE loss, same clip-then-SGD semantics;
 only GEMM scheduling (bmm vs mm) and float accumulation orders differ.
@@ -73,14 +77,17 @@ class ShakespeareMegaRound(GraphedMegaRound):
     EAGER_ENV = "MEGA_SHK_EAGER"
 
     def __init__(self, arena: ParameterArena, bs: int,
-                 max_grad_norm, k_cap: int = 32):
+                 max_grad_norm, k_cap: int = 32, use_bf16: bool = False):
         super().__init__(arena, bs, max_grad_norm, k_cap)
         vc = matches_char_lstm(arena)
         assert vc is not None
         self.V, self.E = vc
+        # bf16-stored recurrent weights in both layers' recurrences
+        # (ops/lstm._LSTMSeq); everything else in the round stays fp32
+        self.use_bf16 = bool(use_bf16)
 
     def _graph_key(self, K, steps, store):
-        return (K, steps, self.bs, store.x.shape[1])
+        return (K, steps, self.bs, store.x.shape[1], self.use_bf16)
 
     def _step(self, flat, x, y, K, loss_dev):
         """One batched training step's forward + loss (autograd does the
@@ -102,12 +109,12 @@ class ShakespeareMegaRound(GraphedMegaRound):
         xp0 = torch.baddbmm(b0.unsqueeze(1), e,
                             v["net.lstm.weight_ih_l0"].transpose(1, 2))
         h0 = _LSTMSeq.apply(xp0.view(R, T, 4 * H),
-                            v["net.lstm.weight_hh_l0"], bs)
+                            v["net.lstm.weight_hh_l0"], bs, self.use_bf16)
         b1 = (v["net.lstm.bias_ih_l1"] + v["net.lstm.bias_hh_l1"])
         xp1 = torch.baddbmm(b1.unsqueeze(1), h0.view(K, bs * T, H),
                             v["net.lstm.weight_ih_l1"].transpose(1, 2))
         h1 = _LSTMSeq.apply(xp1.view(R, T, 4 * H),
-                            v["net.lstm.weight_hh_l1"], bs)
+                            v["net.lstm.weight_hh_l1"], bs, self.use_bf16)
         logits = torch.baddbmm(v["net.fc.bias"].unsqueeze(1),
                                h1.view(K, bs * T, H),
                                v["net.fc.weight"].transpose(1, 2))

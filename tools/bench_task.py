@@ -26,6 +26,9 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--users", type=int, default=None)
     ap.add_argument("--samples", type=int, default=None)
+    ap.add_argument("--mixed-precision", choices=["fp32", "bf16"],
+                    default="fp32",
+                    help="client_config.mixed_precision (fp32 = unset)")
     args = ap.parse_args()
 
     from msrflute_amd.comm import runtime as rt_mod
@@ -44,6 +47,9 @@ def main():
     sc.update(max_iteration=args.warmup + args.steps, val_freq=10 ** 9,
               rec_freq=10 ** 9, initial_val=False, initial_rec=False,
               seed=1234)
+
+    if args.mixed_precision != "fp32":
+        cfg["client_config"]["mixed_precision"] = args.mixed_precision
 
     fn, kw = cd.TASKS[args.task]
     kw = dict(kw)
