@@ -354,15 +354,123 @@ __global__ void k_pool_drop_fwd_mb(const float* __restrict__ r2, int bs,
   }
 }
 
+// widest vector (in floats) that an access at byte address `a` and at any
+// multiple of 16 B past it may use.  The per-client stacks put client k at
+// k*P floats, and P need not be a multiple of 4 (P*4 mod 16 = 8 at C = 62),
+// so the fc1 kernels pick their global access width per block from the
+// actual addresses: 16 B, two 8 B halves, or dwords.
+typedef __attribute__((ext_vector_type(2))) float f32x2;
+__device__ __forceinline__ int addr_vec(unsigned long long a) {
+  return (a & 15) == 0 ? 4 : ((a & 7) == 0 ? 2 : 1);
+}
+template <int VEC>
+__device__ __forceinline__ void ld_vec(const float* __restrict__ p,
+                                       float* v) {
+  if (VEC == 4) {
+    f32x4 t = *reinterpret_cast<const f32x4*>(p);
+    v[0] = t[0]; v[1] = t[1]; v[2] = t[2]; v[3] = t[3];
+  } else if (VEC == 2) {
+    f32x2 t = *reinterpret_cast<const f32x2*>(p);
+    v[0] = t[0]; v[1] = t[1];
+  } else {
+    v[0] = p[0];
+  }
+}
+template <int VEC>
+__device__ __forceinline__ void st_vec(float* __restrict__ p,
+                                       const float* v) {
+  if (VEC == 4)
+    *reinterpret_cast<f32x4*>(p) = f32x4{v[0], v[1], v[2], v[3]};
+  else if (VEC == 2)
+    *reinterpret_cast<f32x2*>(p) = f32x2{v[0], v[1]};
+  else
+    p[0] = v[0];
+}
+
 // fc1 forward as split-K MFMA GEMM: z3^T[j,b] = sum_k W3[j,k]*a2[b,k],
 // M=128 (j), N=32 (b, masked to bs), K=9216 split into FC1_SPLIT chunks;
 // per-chunk partials land in the slab and k_fc1_fwd_reduce* folds them.
-// grid = K * FC1_SPLIT blocks.
+// grid = K * FC1_SPLIT blocks.  A block walks its 144-k chunk in three
+// 48-k sub-chunks: the next sub-chunk's global loads (VEC floats each)
+// are issued into registers before the current sub-chunk's MFMAs, and
+// the 31.25 KB LDS image lets five blocks share a CU, so all K * 64
+// blocks are co-resident and one block's fill overlaps another's math.
+// Every partial is still one k-ordered MFMA chain over its 144 k.
 #define FC1_SPLIT 64
 #define FC1_CH (9216 / FC1_SPLIT)  /* 144 k per chunk */
-#define FC1_LD (FC1_CH + 1)        /* LDS row stride 145: odd multiplier of
-                                      16 mod 32 -> conflict-free group reads */
-__global__ __launch_bounds__(256)
+#define FC1_SUB 48                 /* k per LDS sub-chunk */
+#define FC1_LD (FC1_SUB + 2)       /* LDS row stride 50 = 18 mod 32: the 32
+                                      lanes of a ds_read_b32 group (16 rows x
+                                      2 k) hit 32 distinct banks */
+template <int VEC>
+__device__ __forceinline__ void fc1_fwd_body(
+    const float* __restrict__ w3, const float* __restrict__ a2k, int bs,
+    int k_base, float* lw, float* la, f32x4 (&acc)[2][2]) {
+  constexpr int PER_ROW = FC1_SUB / VEC;          // items per row
+  constexpr int NW = 128 * PER_ROW / 256;         // W items per thread
+  constexpr int A_ITEMS = 32 * PER_ROW;
+  constexpr int NA = (A_ITEMS + 255) / 256;       // a2 items per thread
+  float rw[NW][VEC], ra[NA][VEC];
+  auto fetch = [&](int sub) {
+    int kb = k_base + sub * FC1_SUB;
+    #pragma unroll
+    for (int n = 0; n < NW; ++n) {
+      int i = threadIdx.x + n * 256;
+      int row = i / PER_ROW, c = i % PER_ROW;
+      ld_vec<VEC>(w3 + (row * 9216 + kb + c * VEC), rw[n]);
+    }
+    #pragma unroll
+    for (int n = 0; n < NA; ++n) {
+      int i = threadIdx.x + n * 256;
+      int bu = i / PER_ROW, c = i % PER_ROW;
+      #pragma unroll
+      for (int e = 0; e < VEC; ++e) ra[n][e] = 0.f;
+      if (i < A_ITEMS && bu < bs)
+        ld_vec<VEC>(a2k + (bu * 9216 + kb + c * VEC), ra[n]);
+    }
+  };
+  int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  int kc = lane >> 4, il = lane & 15;
+  fetch(0);
+  #pragma unroll 1
+  for (int sub = 0; sub < FC1_CH / FC1_SUB; ++sub) {
+    #pragma unroll
+    for (int n = 0; n < NW; ++n) {
+      int i = threadIdx.x + n * 256;
+      int row = i / PER_ROW, c = i % PER_ROW;
+      #pragma unroll
+      for (int e = 0; e < VEC; ++e)
+        lw[row * FC1_LD + c * VEC + e] = rw[n][e];
+    }
+    #pragma unroll
+    for (int n = 0; n < NA; ++n) {
+      int i = threadIdx.x + n * 256;
+      int bu = i / PER_ROW, c = i % PER_ROW;
+      if (i < A_ITEMS) {
+        #pragma unroll
+        for (int e = 0; e < VEC; ++e)
+          la[bu * FC1_LD + c * VEC + e] = ra[n][e];
+      }
+    }
+    __syncthreads();
+    if (sub + 1 < FC1_CH / FC1_SUB) fetch(sub + 1);
+    #pragma unroll 6
+    for (int k0 = 0; k0 < FC1_SUB; k0 += 4) {
+      int kk = k0 + kc;
+      float a0 = lw[(w * 32 + il) * FC1_LD + kk];
+      float a1v = lw[(w * 32 + 16 + il) * FC1_LD + kk];
+      #pragma unroll
+      for (int u = 0; u < 2; ++u) {
+        float bv = la[(u * 16 + il) * FC1_LD + kk];
+        acc[0][u] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, bv, acc[0][u], 0, 0, 0);
+        acc[1][u] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1v, bv, acc[1][u], 0, 0, 0);
+      }
+    }
+    __syncthreads();
+  }
+}
+
+__global__ __launch_bounds__(256, 3)  // 3 blocks/CU: K*64 = 640 co-resident
 void k_fc1_fwd_mfma_mb(const float* __restrict__ a2,
                        const float* __restrict__ params, long long P,
                        long long ow3, int bs, int K,
@@ -374,31 +482,14 @@ void k_fc1_fwd_mfma_mb(const float* __restrict__ a2,
   int k_base = s * FC1_CH;
   const float* w3 = params + (long long)k * P + ow3;
   const float* a2k = a2 + (long long)k * bs * 9216;
-  for (int i = threadIdx.x; i < 128 * FC1_CH; i += 256) {
-    int row = i / FC1_CH, kk = i % FC1_CH;
-    lw[row * FC1_LD + kk] = w3[(long long)row * 9216 + k_base + kk];
-  }
-  for (int i = threadIdx.x; i < 32 * FC1_CH; i += 256) {
-    int bu = i / FC1_CH, kk = i % FC1_CH;
-    la[bu * FC1_LD + kk] = bu < bs
-        ? a2k[(long long)bu * 9216 + k_base + kk] : 0.f;
-  }
-  __syncthreads();
-  int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  int kc = lane >> 4, il = lane & 15;
   f32x4 acc[2][2] = {{f32x4{0,0,0,0}, f32x4{0,0,0,0}},
                      {f32x4{0,0,0,0}, f32x4{0,0,0,0}}};
-  for (int k0 = 0; k0 < FC1_CH; k0 += 4) {
-    int kk = k0 + kc;
-    float a0 = lw[(w * 32 + il) * FC1_LD + kk];
-    float a1v = lw[(w * 32 + 16 + il) * FC1_LD + kk];
-    #pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      float bv = la[(u * 16 + il) * FC1_LD + kk];
-      acc[0][u] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, bv, acc[0][u], 0, 0, 0);
-      acc[1][u] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1v, bv, acc[1][u], 0, 0, 0);
-    }
-  }
+  int vec = addr_vec((unsigned long long)w3 | (unsigned long long)a2k);
+  if (vec == 4) fc1_fwd_body<4>(w3, a2k, bs, k_base, lw, la, acc);
+  else if (vec == 2) fc1_fwd_body<2>(w3, a2k, bs, k_base, lw, la, acc);
+  else fc1_fwd_body<1>(w3, a2k, bs, k_base, lw, la, acc);
+  int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  int il = lane & 15;
   float* slk = slab + (long long)k * FC1_SPLIT * bs * 128;
   #pragma unroll
   for (int tt = 0; tt < 2; ++tt)
@@ -417,15 +508,33 @@ void k_fc1_fwd_mfma_mb(const float* __restrict__ a2,
 // order (deterministic — no atomics) + bias + relu + dropout(p2) into
 // element i of z3/a3/m3.  Philox key: (seed ^ golden ratio, li, batch
 // offset) with li = b*128 + j the CLIENT-LOCAL element index.
+// The fold wrappers launch FC1R_BLK-thread blocks.  Measured at the
+// benchmark shape (25,600 outputs): 256-thread blocks 11 us, 128 17 us,
+// 64 18 us — spreading the fold over more CUs is slower, so the block
+// stays at 256; the launch bound keeps the Philox state's LDS image small.
+#define FC1R_BLK 256
+#define FC1R_BATCH 64
 template <int SPLIT>
 __device__ __forceinline__ void fc1_reduce_elem(
     const float* __restrict__ slk, float bias, int bs, int b, int j,
     long long i, long long li, float p2, unsigned long long seed,
     unsigned long long offset, float* __restrict__ z3,
     float* __restrict__ a3, unsigned char* __restrict__ m3) {
+  // the loads of a batch of FC1R_BATCH partials are issued before its
+  // first add (one round trip per batch, not one per partial); the adds
+  // run in the fixed order s = 0, 1, …
   float t = bias;
-  for (int s = 0; s < SPLIT; ++s)
-    t += slk[((long long)s * bs + b) * 128 + j];
+  #pragma unroll
+  for (int s0 = 0; s0 < SPLIT; s0 += FC1R_BATCH) {
+    float v[FC1R_BATCH];
+    #pragma unroll
+    for (int n = 0; n < FC1R_BATCH; ++n)
+      if (s0 + n < SPLIT)
+        v[n] = slk[((long long)(s0 + n) * bs + b) * 128 + j];
+    #pragma unroll
+    for (int n = 0; n < FC1R_BATCH; ++n)
+      if (s0 + n < SPLIT) t += v[n];
+  }
   z3[i] = t;
   float r = t > 0.f ? t : 0.f;
   unsigned char keep = 1;
@@ -473,7 +582,7 @@ __device__ __forceinline__ void fc1_reduce_stack(
   }
 }
 
-__global__ void k_fc1_fwd_reduce(const float* __restrict__ slab,
+__global__ __launch_bounds__(FC1R_BLK) void k_fc1_fwd_reduce(const float* __restrict__ slab,
                                  const float* __restrict__ b3, int B,
                                  float p2, unsigned long long seed,
                                  unsigned long long offset,
@@ -483,7 +592,7 @@ __global__ void k_fc1_fwd_reduce(const float* __restrict__ slab,
   fc1_reduce_client<FC1_SPLIT>(slab, b3, B, p2, seed, offset, z3, a3, m3);
 }
 
-__global__ void k_fc1_fwd_reduce_mb(const float* __restrict__ slab,
+__global__ __launch_bounds__(FC1R_BLK) void k_fc1_fwd_reduce_mb(const float* __restrict__ slab,
                                     const float* __restrict__ params,
                                     long long P, long long ob3, int bs,
                                     int K, float p2,
@@ -608,17 +717,22 @@ __global__ void k_fc2_bwd_x_mb(const float* __restrict__ dlogits,
   }
 }
 
-// fc1 backward weights (f32 MFMA): grid = K * 144
-__global__ __launch_bounds__(256)
-void k_fc1_bwd_w_mfma_mb(const float* __restrict__ dz3,
-                         const float* __restrict__ a2,
-                         float* __restrict__ grads, long long P,
-                         long long ow3, int bs, int K) {
-  int k = blockIdx.x / 144;
-  int nblk = blockIdx.x % 144;
-  const float* dz = dz3 + (long long)k * bs * 128;
-  const float* a2k = a2 + (long long)k * bs * 9216;
-  float* dw3 = grads + (long long)k * P + ow3;
+// Column map of the two fc1 backward kernels.  n = 9216 is an OUTPUT
+// dimension in both, so which lane owns which column is free and changes
+// no element's summation chain.  A wave's 64 columns are owned so that a
+// lane reads and writes VEC adjacent columns at once: n-tile nt of lane
+// il is column (nt / VEC) * 16 * VEC + VEC * il + nt % VEC.  VEC = 4: one
+// 16 B access of columns 4*il .. 4*il+3, a wave instruction covers 256
+// contiguous bytes per row; VEC = 2: two 8 B halves 32 columns apart;
+// VEC = 1: the dword map nt * 16 + il.
+#define FC1B_COL(VEC, g, il) ((g) * 16 * (VEC) + (VEC) * (il))
+
+// fc1 backward weights (f32 MFMA): grid = K * 144.  Block 0 of every
+// client also writes the 128 bias sums db3[j] = sum_b dz3[b][j].
+template <int VEC>
+__device__ __forceinline__ void fc1_bwd_w_body(
+    const float* __restrict__ dz, const float* __restrict__ a2k,
+    float* __restrict__ dw3, int bs, int nblk) {
   int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   int kc = lane >> 4, il = lane & 15;
   f32x4 acc[2][4] = {{f32x4{0,0,0,0}, f32x4{0,0,0,0}, f32x4{0,0,0,0}, f32x4{0,0,0,0}},
@@ -626,14 +740,25 @@ void k_fc1_bwd_w_mfma_mb(const float* __restrict__ dz3,
   for (int k0 = 0; k0 < ((bs + 3) & ~3); k0 += 4) {
     int b = k0 + kc;
     bool kv = b < bs;
-    float a0 = kv ? dz[(long long)b * 128 + w * 32 + il] : 0.f;
-    float a1v = kv ? dz[(long long)b * 128 + w * 32 + 16 + il] : 0.f;
+    // rows >= bs read the last valid row and are zeroed by selects, so no
+    // load sits behind a branch (and a full wait)
+    int bl = kv ? b : bs - 1;
+    float a0 = dz[bl * 128 + w * 32 + il];
+    float a1v = dz[bl * 128 + w * 32 + 16 + il];
+    float bv[4];
+    #pragma unroll
+    for (int g = 0; g < 4 / VEC; ++g)
+      ld_vec<VEC>(a2k + (bl * 9216 + nblk * 64 + FC1B_COL(VEC, g, il)),
+                  bv + g * VEC);
+    if (!kv) {
+      a0 = 0.f; a1v = 0.f;
+      #pragma unroll
+      for (int nt = 0; nt < 4; ++nt) bv[nt] = 0.f;
+    }
     #pragma unroll
     for (int nt = 0; nt < 4; ++nt) {
-      long long n = (long long)nblk * 64 + nt * 16 + il;
-      float bv = kv ? a2k[(long long)b * 9216 + n] : 0.f;
-      acc[0][nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, bv, acc[0][nt], 0, 0, 0);
-      acc[1][nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1v, bv, acc[1][nt], 0, 0, 0);
+      acc[0][nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, bv[nt], acc[0][nt], 0, 0, 0);
+      acc[1][nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1v, bv[nt], acc[1][nt], 0, 0, 0);
     }
   }
   #pragma unroll
@@ -642,48 +767,83 @@ void k_fc1_bwd_w_mfma_mb(const float* __restrict__ dz3,
     #pragma unroll
     for (int r = 0; r < 4; ++r)
       #pragma unroll
-      for (int nt = 0; nt < 4; ++nt)
-        dw3[(long long)(j + r) * 9216 + nblk * 64 + nt * 16 + il] =
-            acc[tt][nt][r];
+      for (int g = 0; g < 4 / VEC; ++g) {
+        float v[VEC];
+        #pragma unroll
+        for (int e = 0; e < VEC; ++e) v[e] = acc[tt][g * VEC + e][r];
+        st_vec<VEC>(dw3 + ((j + r) * 9216 + nblk * 64 +
+                           FC1B_COL(VEC, g, il)), v);
+      }
   }
 }
 
-__global__ void k_fc1_bwd_b_mb(const float* __restrict__ dz3,
-                               float* __restrict__ grads, long long P,
-                               long long ob3, int bs, int K) {
-  int k = blockIdx.x;
-  int j = threadIdx.x;
-  if (j >= 128) return;
-  const float* dz = dz3 + (long long)k * bs * 128;
-  float s = 0.f;
-  for (int b = 0; b < bs; ++b) s += dz[(long long)b * 128 + j];
-  grads[(long long)k * P + ob3 + j] = s;
-}
-
-// fc1 backward data (f32 MFMA): grid = K * 144
+// dw3 rows live at gw + k*Pw + ow3, the bias sums at gb + k*Pb + ob3 (the
+// round passes the gradient stack twice; the debug launcher two buffers)
 __global__ __launch_bounds__(256)
-void k_fc1_bwd_x_mfma_mb(const float* __restrict__ dz3,
-                         const float* __restrict__ params, long long P,
-                         long long ow3, int bs, int K,
-                         float* __restrict__ da2) {
+void k_fc1_bwd_w_mfma_mb(const float* __restrict__ dz3,
+                         const float* __restrict__ a2,
+                         float* gw, long long Pw, long long ow3,
+                         float* gb, long long Pb, long long ob3,
+                         int bs, int K) {
   int k = blockIdx.x / 144;
   int nblk = blockIdx.x % 144;
   const float* dz = dz3 + (long long)k * bs * 128;
-  const float* w3 = params + (long long)k * P + ow3;
-  float* da = da2 + (long long)k * bs * 9216;
-  int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const float* a2k = a2 + (long long)k * bs * 9216;
+  float* dw3 = gw + (long long)k * Pw + ow3;
+  int vec = addr_vec((unsigned long long)a2k | (unsigned long long)dw3);
+  if (vec == 4) fc1_bwd_w_body<4>(dz, a2k, dw3, bs, nblk);
+  else if (vec == 2) fc1_bwd_w_body<2>(dz, a2k, dw3, bs, nblk);
+  else fc1_bwd_w_body<1>(dz, a2k, dw3, bs, nblk);
+  if (nblk == 0 && threadIdx.x < 128) {
+    int j = threadIdx.x;
+    float s = 0.f;
+    for (int b = 0; b < bs; ++b) s += dz[(long long)b * 128 + j];
+    gb[(long long)k * Pb + ob3 + j] = s;
+  }
+}
+
+// fc1 backward data (f32 MFMA): grid = K * FC1X_BLKS blocks of FC1X_WAVES
+// waves; a wave owns 64 columns (2 x 4 accumulators) and walks j = 0..127
+// in order, FC1X_GRP k-steps of loads in flight at a time.
+#define FC1X_WAVES 2
+#define FC1X_GRP 8
+#define FC1X_BLKS (9216 / (64 * FC1X_WAVES))
+template <int VEC>
+__device__ __forceinline__ void fc1_bwd_x_body(
+    const float* __restrict__ dz, const float* __restrict__ w3,
+    float* __restrict__ da, int bs, int col0) {
+  int lane = threadIdx.x & 63;
   int kc = lane >> 4, il = lane & 15;
-  f32x4 acc[2] = {f32x4{0,0,0,0}, f32x4{0,0,0,0}};
-  for (int k0 = 0; k0 < 128; k0 += 4) {
-    int j = k0 + kc;
-    long long n = (long long)nblk * 64 + w * 16 + il;
-    float bv = w3[(long long)j * 9216 + n];
+  f32x4 acc[2][4] = {{f32x4{0,0,0,0}, f32x4{0,0,0,0}, f32x4{0,0,0,0}, f32x4{0,0,0,0}},
+                     {f32x4{0,0,0,0}, f32x4{0,0,0,0}, f32x4{0,0,0,0}, f32x4{0,0,0,0}}};
+  // FC1X_GRP k-steps at a time: all of the group's loads are issued into
+  // registers, then its MFMAs run in k order.  Rows >= bs read a clamped
+  // (valid) dz row and are zeroed by a select: a branch around a load
+  // would put a full wait behind it.
+  int r0 = (il < bs ? il : bs - 1) * 128 + kc;
+  int r1 = (16 + il < bs ? 16 + il : bs - 1) * 128 + kc;
+  #pragma unroll 1
+  for (int k0 = 0; k0 < 128; k0 += 4 * FC1X_GRP) {
+    float bv[FC1X_GRP][4], av[FC1X_GRP][2];
     #pragma unroll
-    for (int tt = 0; tt < 2; ++tt) {
-      int bu = tt * 16 + il;
-      float a = bu < bs ? dz[(long long)bu * 128 + j] : 0.f;
-      acc[tt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, bv, acc[tt], 0, 0, 0);
+    for (int u = 0; u < FC1X_GRP; ++u) {
+      int j = k0 + 4 * u + kc;
+      #pragma unroll
+      for (int g = 0; g < 4 / VEC; ++g)
+        ld_vec<VEC>(w3 + (j * 9216 + col0 + FC1B_COL(VEC, g, il)),
+                    bv[u] + g * VEC);
+      av[u][0] = dz[r0 + k0 + 4 * u];
+      av[u][1] = dz[r1 + k0 + 4 * u];
     }
+    #pragma unroll
+    for (int u = 0; u < FC1X_GRP; ++u)
+      #pragma unroll
+      for (int tt = 0; tt < 2; ++tt) {
+        float a = tt * 16 + il < bs ? av[u][tt] : 0.f;
+        #pragma unroll
+        for (int nt = 0; nt < 4; ++nt)
+          acc[tt][nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, bv[u][nt], acc[tt][nt], 0, 0, 0);
+      }
   }
   #pragma unroll
   for (int tt = 0; tt < 2; ++tt) {
@@ -691,10 +851,33 @@ void k_fc1_bwd_x_mfma_mb(const float* __restrict__ dz3,
     #pragma unroll
     for (int r = 0; r < 4; ++r) {
       if (bu + r >= bs) continue;
-      da[(long long)(bu + r) * 9216 + (long long)nblk * 64 + w * 16 + il] =
-          acc[tt][r];
+      #pragma unroll
+      for (int g = 0; g < 4 / VEC; ++g) {
+        float v[VEC];
+        #pragma unroll
+        for (int e = 0; e < VEC; ++e) v[e] = acc[tt][g * VEC + e][r];
+        st_vec<VEC>(da + ((bu + r) * 9216 + col0 + FC1B_COL(VEC, g, il)),
+                    v);
+      }
     }
   }
+}
+
+__global__ __launch_bounds__(64 * FC1X_WAVES)
+void k_fc1_bwd_x_mfma_mb(const float* __restrict__ dz3,
+                         const float* __restrict__ params, long long P,
+                         long long ow3, int bs, int K,
+                         float* __restrict__ da2) {
+  int k = blockIdx.x / FC1X_BLKS;
+  int nblk = blockIdx.x % FC1X_BLKS;
+  const float* dz = dz3 + (long long)k * bs * 128;
+  const float* w3 = params + (long long)k * P + ow3;
+  float* da = da2 + (long long)k * bs * 9216;
+  int col0 = (nblk * FC1X_WAVES + (int)(threadIdx.x >> 6)) * 64;
+  int vec = addr_vec((unsigned long long)w3 | (unsigned long long)da);
+  if (vec == 4) fc1_bwd_x_body<4>(dz, w3, da, bs, col0);
+  else if (vec == 2) fc1_bwd_x_body<2>(dz, w3, da, bs, col0);
+  else fc1_bwd_x_body<1>(dz, w3, da, bs, col0);
 }
 
 __global__ void k_pool_drop_bwd_mb(const float* __restrict__ da2,
@@ -1081,6 +1264,20 @@ __global__ void k_sumsq_mb(const float* __restrict__ grads, long long P,
   }
 }
 
+__device__ __forceinline__ float clip_scale(const double* __restrict__ acc,
+                                            int k, float max_norm,
+                                            float eps) {
+  float norm = (float)sqrt(acc[2 * k + 1]);
+  return (max_norm > 0.f && norm > max_norm) ? max_norm / (norm + eps) : 1.f;
+}
+
+// STORE_G: also write the clipped gradient back.  The CNN mega round
+// never reads it (the next batch-step's backward kernels and
+// k_pseudo_grad_mb overwrite the whole stack), so it runs the variant
+// without that store; the stand-alone entry keeps it.  i only grows, so
+// a thread re-derives its client and the scale when it crosses a segment
+// end, not per element.
+template <bool STORE_G>
 __global__ void k_clip_sgd_mb(float* __restrict__ params,
                               float* __restrict__ grads, long long P, int K,
                               const double* __restrict__ acc, float max_norm,
@@ -1088,14 +1285,19 @@ __global__ void k_clip_sgd_mb(float* __restrict__ params,
                               float* __restrict__ stats_out) {
   long long total = (long long)K * P;
   float lr = lr_t[0];
-  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
-       i < total; i += (long long)gridDim.x * blockDim.x) {
-    int k = (int)(i / P);
-    float norm = (float)sqrt(acc[2 * k + 1]);
-    float scale = (max_norm > 0.f && norm > max_norm)
-                      ? max_norm / (norm + eps) : 1.f;
+  long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+  if (i >= total) return;
+  int k = (int)(i / P);
+  long long seg_end = (long long)(k + 1) * P;
+  float scale = clip_scale(acc, k, max_norm, eps);
+  for (; i < total; i += (long long)gridDim.x * blockDim.x) {
+    if (i >= seg_end) {
+      k = (int)(i / P);
+      seg_end = (long long)(k + 1) * P;
+      scale = clip_scale(acc, k, max_norm, eps);
+    }
     float gv = grads[i] * scale;
-    grads[i] = gv;
+    if constexpr (STORE_G) grads[i] = gv;
     params[i] -= lr * gv;
   }
 }
@@ -1362,7 +1564,7 @@ void k_fc1_fwd_mfma_mb_bf16(const float* __restrict__ a2,
     }
 }
 
-__global__ void k_fc1_fwd_reduce_bf16(const float* __restrict__ slab,
+__global__ __launch_bounds__(FC1R_BLK) void k_fc1_fwd_reduce_bf16(const float* __restrict__ slab,
                                       const float* __restrict__ b3, int B,
                                       float p2, unsigned long long seed,
                                       unsigned long long offset,
@@ -1372,7 +1574,7 @@ __global__ void k_fc1_fwd_reduce_bf16(const float* __restrict__ slab,
   fc1_reduce_client<FC1B_SPLIT>(slab, b3, B, p2, seed, offset, z3, a3, m3);
 }
 
-__global__ void k_fc1_fwd_reduce_mb_bf16(const float* __restrict__ slab,
+__global__ __launch_bounds__(FC1R_BLK) void k_fc1_fwd_reduce_mb_bf16(const float* __restrict__ slab,
                                          const float* __restrict__ params,
                                          long long P, long long ob3, int bs,
                                          int K, float p2,
@@ -1481,15 +1683,16 @@ extern "C" void launch_cnn_epoch(
                          0, s, ws.a2, params, P, o.w3, B, K, ws.wsl);
       EPOCH_CHK("k_fc1_fwd_mfma_mb_bf16");
       hipLaunchKernelGGL(k_fc1_fwd_reduce_bf16,
-                         dim3((B * 128 + FBLK - 1) / FBLK),
-                         dim3(FBLK), 0, s, ws.wsl, params + o.b3, B, p2, seed,
+                         dim3((B * 128 + FC1R_BLK - 1) / FC1R_BLK),
+                         dim3(FC1R_BLK), 0, s, ws.wsl, params + o.b3, B, p2, seed,
                          off, ws.z3, ws.a3, ws.m3);
     } else {
       hipLaunchKernelGGL(k_fc1_fwd_mfma_mb, dim3(FC1_SPLIT), dim3(FBLK), 0, s,
                          ws.a2, params, P, o.w3, B, K, ws.wsl);
       EPOCH_CHK("k_fc1_fwd_mfma_mb");
-      hipLaunchKernelGGL(k_fc1_fwd_reduce, dim3((B * 128 + FBLK - 1) / FBLK),
-                         dim3(FBLK), 0, s, ws.wsl, params + o.b3, B, p2, seed,
+      hipLaunchKernelGGL(k_fc1_fwd_reduce,
+                         dim3((B * 128 + FC1R_BLK - 1) / FC1R_BLK),
+                         dim3(FC1R_BLK), 0, s, ws.wsl, params + o.b3, B, p2, seed,
                          off, ws.z3, ws.a3, ws.m3);
     }
     EPOCH_CHK("k_fc1_fwd_reduce");
@@ -1506,12 +1709,10 @@ extern "C" void launch_cnn_epoch(
                        ws.m3, B, K, C, p2, ws.dz3);
     EPOCH_CHK("k_fc2_bwd_x_mb");
     hipLaunchKernelGGL(k_fc1_bwd_w_mfma_mb, dim3(144), dim3(FBLK), 0, s,
-                       ws.dz3, ws.a2, grads, P, o.w3, B, K);
+                       ws.dz3, ws.a2, grads, P, o.w3, grads, P, o.b3, B, K);
     EPOCH_CHK("k_fc1_bwd_w_mfma_mb");
-    hipLaunchKernelGGL(k_fc1_bwd_b_mb, dim3(K), dim3(128), 0, s,
-                       ws.dz3, grads, P, o.b3, B, K);
-    EPOCH_CHK("k_fc1_bwd_b_mb");
-    hipLaunchKernelGGL(k_fc1_bwd_x_mfma_mb, dim3(144), dim3(FBLK), 0, s,
+    hipLaunchKernelGGL(k_fc1_bwd_x_mfma_mb, dim3(FC1X_BLKS),
+                       dim3(64 * FC1X_WAVES), 0, s,
                        ws.dz3, params, P, o.w3, B, K, ws.da2);
     EPOCH_CHK("k_fc1_bwd_x_mfma_mb");
     hipLaunchKernelGGL(k_pool_drop_bwd_mb, dim3((B * 9216 + FBLK - 1) / FBLK),
@@ -1655,15 +1856,17 @@ extern "C" void launch_cnn_round_mega(
       hipLaunchKernelGGL(k_fc1_fwd_mfma_mb_bf16, dim3(K * 36), dim3(FBLK),
                          0, s, a2, params_stack, P, o.w3, bs, K, slab);
       hipLaunchKernelGGL(k_fc1_fwd_reduce_mb_bf16,
-                         dim3((int)(((long long)G * 128 + FBLK - 1) / FBLK)),
-                         dim3(FBLK), 0, s, slab, params_stack, P, o.b3, bs,
+                         dim3((int)(((long long)G * 128 + FC1R_BLK - 1) /
+                                    FC1R_BLK)),
+                         dim3(FC1R_BLK), 0, s, slab, params_stack, P, o.b3, bs,
                          K, p2, seeds_dev, off, z3, a3, m3);
     } else {
       hipLaunchKernelGGL(k_fc1_fwd_mfma_mb, dim3(K * FC1_SPLIT), dim3(FBLK),
                          0, s, a2, params_stack, P, o.w3, bs, K, slab);
       hipLaunchKernelGGL(k_fc1_fwd_reduce_mb,
-                         dim3((int)(((long long)G * 128 + FBLK - 1) / FBLK)),
-                         dim3(FBLK), 0, s, slab, params_stack, P, o.b3, bs,
+                         dim3((int)(((long long)G * 128 + FC1R_BLK - 1) /
+                                    FC1R_BLK)),
+                         dim3(FC1R_BLK), 0, s, slab, params_stack, P, o.b3, bs,
                          K, p2, seeds_dev, off, z3, a3, m3);
     }
     hipLaunchKernelGGL(k_fc2_loss_fwd_mb, dim3(G), dim3(FBLK),
@@ -1677,10 +1880,10 @@ extern "C" void launch_cnn_round_mega(
                        dim3(FBLK), 0, s, dlogits, params_stack, P, o.w4,
                        z3, m3, bs, K, C, p2, dz3);
     hipLaunchKernelGGL(k_fc1_bwd_w_mfma_mb, dim3(K * 144), dim3(FBLK), 0, s,
-                       dz3, a2, grads_stack, P, o.w3, bs, K);
-    hipLaunchKernelGGL(k_fc1_bwd_b_mb, dim3(K), dim3(128), 0, s,
-                       dz3, grads_stack, P, o.b3, bs, K);
-    hipLaunchKernelGGL(k_fc1_bwd_x_mfma_mb, dim3(K * 144), dim3(FBLK), 0, s,
+                       dz3, a2, grads_stack, P, o.w3, grads_stack, P, o.b3,
+                       bs, K);
+    hipLaunchKernelGGL(k_fc1_bwd_x_mfma_mb, dim3(K * FC1X_BLKS),
+                       dim3(64 * FC1X_WAVES), 0, s,
                        dz3, params_stack, P, o.w3, bs, K, da2);
     hipLaunchKernelGGL(k_pool_drop_bwd_mb,
                        dim3((int)(((long long)G * 9216 + FBLK - 1) / FBLK)),
@@ -1713,7 +1916,7 @@ extern "C" void launch_cnn_round_mega(
                        grads_stack, P, blocks_per_k, acc2k);
     hipLaunchKernelGGL(k_stats_mb, dim3((K + 63) / 64), dim3(64), 0, s,
                        acc2k, K, max_norm, 1e-6f, stats_out);
-    hipLaunchKernelGGL(k_clip_sgd_mb, dim3(gkp), dim3(FBLK), 0, s,
+    hipLaunchKernelGGL(k_clip_sgd_mb<false>, dim3(gkp), dim3(FBLK), 0, s,
                        params_stack, grads_stack, P, K, acc2k, max_norm,
                        1e-6f, lr_t, stats_out);
   }
@@ -1742,7 +1945,7 @@ extern "C" void launch_mega_clip_sgd(float* params_stack, float* grads_stack,
                      acc2k, K, max_norm, 1e-6f, stats_out);
   long long kp = (long long)K * P;
   int gkp = (int)((kp + FBLK - 1) / FBLK); if (gkp > 4096) gkp = 4096;
-  hipLaunchKernelGGL(k_clip_sgd_mb, dim3(gkp), dim3(FBLK), 0, s,
+  hipLaunchKernelGGL(k_clip_sgd_mb<true>, dim3(gkp), dim3(FBLK), 0, s,
                      params_stack, grads_stack, P, K, acc2k, max_norm,
                      1e-6f, lr_t, stats_out);
 }
@@ -1813,8 +2016,9 @@ void launch_fc1_fwd_mfma(const float* a2, const float* w3, const float* b3,
   hipLaunchKernelGGL(k_fc1_fwd_mfma_mb, dim3(K * FC1_SPLIT), dim3(FBLK), 0, s,
                      a2, w3, W3N, 0LL, bs, K, slab);
   for (int k = 0; k < K; ++k)
-    hipLaunchKernelGGL(k_fc1_fwd_reduce, dim3((bs * 128 + FBLK - 1) / FBLK),
-                       dim3(FBLK), 0, s,
+    hipLaunchKernelGGL(k_fc1_fwd_reduce,
+                       dim3((bs * 128 + FC1R_BLK - 1) / FC1R_BLK),
+                       dim3(FC1R_BLK), 0, s,
                        slab + (long long)k * FC1_SPLIT * bs * 128,
                        b3 + k * 128, bs, p2, seed, offset,
                        z3 + k * bs * 128, a3 + k * bs * 128,
@@ -1823,13 +2027,12 @@ void launch_fc1_fwd_mfma(const float* a2, const float* w3, const float* b3,
 void launch_fc1_bwd_w_mfma(const float* dz3, const float* a2, int bs, int K,
                            float* dw3, float* db3, hipStream_t s) {
   hipLaunchKernelGGL(k_fc1_bwd_w_mfma_mb, dim3(K * 144), dim3(FBLK), 0, s,
-                     dz3, a2, dw3, W3N, 0LL, bs, K);
-  hipLaunchKernelGGL(k_fc1_bwd_b_mb, dim3(K), dim3(128), 0, s,
-                     dz3, db3, 128LL, 0LL, bs, K);
+                     dz3, a2, dw3, W3N, 0LL, db3, 128LL, 0LL, bs, K);
 }
 void launch_fc1_bwd_x_mfma(const float* dz3, const float* w3, int bs, int K,
                            float* da2, hipStream_t s) {
-  hipLaunchKernelGGL(k_fc1_bwd_x_mfma_mb, dim3(K * 144), dim3(FBLK), 0, s,
+  hipLaunchKernelGGL(k_fc1_bwd_x_mfma_mb, dim3(K * FC1X_BLKS),
+                     dim3(64 * FC1X_WAVES), 0, s,
                      dz3, w3, W3N, 0LL, bs, K, da2);
 }
 void launch_mfma_bf16_probe(const void* A, const void* B, float* D,
@@ -1847,7 +2050,8 @@ void launch_fc1_fwd_mfma_bf16(const float* a2, const float* w3,
                      0, s, a2, w3, W3N, 0LL, bs, K, slab);
   for (int k = 0; k < K; ++k)
     hipLaunchKernelGGL(k_fc1_fwd_reduce_bf16,
-                       dim3((bs * 128 + FBLK - 1) / FBLK), dim3(FBLK), 0, s,
+                       dim3((bs * 128 + FC1R_BLK - 1) / FC1R_BLK),
+                       dim3(FC1R_BLK), 0, s,
                        slab + (long long)k * FC1B_SPLIT * bs * 128,
                        b3 + k * 128, bs, p2, seed, offset,
                        z3 + k * bs * 128, a3 + k * bs * 128,
