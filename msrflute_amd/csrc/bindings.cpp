@@ -503,6 +503,58 @@ torch::Tensor dbg_conv2_fwd_mfma(torch::Tensor a1, torch::Tensor w2,
   return r2;
 }
 
+// conv2 forward with the pool + dropout epilogue: (a2, pidx, m2) of
+// K clients x bs rows; seeds is an int64 tensor of K dropout seeds
+std::vector<torch::Tensor> dbg_conv2_fwd_pool_mfma(
+    torch::Tensor a1, torch::Tensor w2, torch::Tensor b2, int64_t bs,
+    int64_t K, double p1, torch::Tensor seeds, int64_t offset) {
+  check_flat(a1, "a1"); check_flat(w2, "w2"); check_flat(b2, "b2");
+  TORCH_CHECK(K >= 1 && bs >= 1 && bs <= 32);
+  long long B = K * bs;
+  TORCH_CHECK(w2.numel() == K * 18432 && b2.numel() == K * 64 &&
+              a1.numel() >= B * 21632);
+  TORCH_CHECK(seeds.scalar_type() == torch::kInt64 && seeds.numel() == K,
+              "seeds must be K int64 values");
+  auto seeds_dev = seeds.to(a1.device()).contiguous();
+  auto w2t = torch::empty_like(w2);
+  auto w2rot = torch::empty_like(w2);
+  auto a2 = torch::empty({B * 9216}, a1.options());
+  auto pidx = torch::empty({B * 9216}, a1.options().dtype(torch::kUInt8));
+  auto m2 = torch::empty({B * 9216}, a1.options().dtype(torch::kUInt8));
+  launch_w2_layouts(w2.data_ptr<float>(), (int)K, w2t.data_ptr<float>(),
+                    w2rot.data_ptr<float>(), cur_stream());
+  launch_conv2_fwd_pool_mfma(
+      a1.data_ptr<float>(), w2t.data_ptr<float>(), b2.data_ptr<float>(),
+      (int)bs, (int)K, (float)p1,
+      reinterpret_cast<const long long*>(seeds_dev.data_ptr<int64_t>()),
+      (unsigned long long)offset, a2.data_ptr<float>(),
+      pidx.data_ptr<unsigned char>(), m2.data_ptr<unsigned char>(),
+      cur_stream());
+  return {a2, pidx, m2};
+}
+
+// pool/dropout backward with the conv2 bias sums: (dz2, db2)
+std::vector<torch::Tensor> dbg_pool_drop_bwd_bias(
+    torch::Tensor da2, torch::Tensor pidx, torch::Tensor m2, int64_t bs,
+    int64_t K, double p1) {
+  check_flat(da2, "da2");
+  TORCH_CHECK(K >= 1 && bs >= 1);
+  long long B = K * bs;
+  TORCH_CHECK(da2.numel() == B * 9216);
+  for (const torch::Tensor* t : {&pidx, &m2})
+    TORCH_CHECK(t->is_cuda() && t->is_contiguous() &&
+                t->scalar_type() == torch::kUInt8 &&
+                t->numel() == B * 9216, "pidx / m2 must be uint8 [B*9216]");
+  auto dz2 = torch::empty({B * 36864}, da2.options());
+  auto db2 = torch::empty({K * 64}, da2.options());
+  launch_pool_drop_bwd_bias(da2.data_ptr<float>(),
+                            pidx.data_ptr<unsigned char>(),
+                            m2.data_ptr<unsigned char>(), (int)bs, (int)K,
+                            (float)p1, dz2.data_ptr<float>(),
+                            db2.data_ptr<float>(), cur_stream());
+  return {dz2, db2};
+}
+
 torch::Tensor dbg_conv2_fwd_mfma_bf16(torch::Tensor a1, torch::Tensor w2,
                                       torch::Tensor b2, int64_t B) {
   check_flat(a1, "a1"); check_flat(w2, "w2"); check_flat(b2, "b2");
@@ -818,6 +870,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("dz2"), py::arg("a1"), py::arg("B"), py::arg("K") = 1);
   m.def("dbg_fc1_fwd_mfma_bf16", &dbg_fc1_fwd_mfma_bf16);
   m.def("dbg_conv2_fwd_mfma", &dbg_conv2_fwd_mfma);
+  m.def("dbg_conv2_fwd_pool_mfma", &dbg_conv2_fwd_pool_mfma);
+  m.def("dbg_pool_drop_bwd_bias", &dbg_pool_drop_bwd_bias);
   m.def("dbg_conv2_bwd_x_mfma", &dbg_conv2_bwd_x_mfma);
   m.def("dbg_conv2_bwd_w_mfma", &dbg_conv2_bwd_w_mfma,
         py::arg("dz2"), py::arg("a1"), py::arg("B"), py::arg("K") = 1);

@@ -18,8 +18,9 @@
 // where a per-client grid (120 blocks) underfills the 256-CU chip.  The
 // per-client epoch (launch_cnn_epoch) launches the same kernels at K = 1
 // with bs := the batch's actual row count and the client's own arena as
-// the stack.  Only the four ops that read per-client metadata (gather,
-// pool dropout, fc1 reduce, loss) have two thin __global__ wrappers
+// the stack.  Only the ops that read per-client metadata (gather, the
+// conv2 forward's pool/dropout epilogue, the bf16 path's pool dropout,
+// fc1 reduce, loss) have two thin __global__ wrappers
 // around one __device__ body: the mega wrapper reads seeds[k]/counts[k]
 // from device arrays, the per-client one takes them as launch arguments
 // so that path uploads nothing.
@@ -125,8 +126,14 @@ __global__ void k_gather_mb(const float* __restrict__ shard_x,
                             const long long* __restrict__ order_offs,
                             const long long* __restrict__ counts,
                             int t, int bs, int K,
-                            float* __restrict__ xb, int* __restrict__ yb) {
+                            float* __restrict__ xb, int* __restrict__ yb,
+                            double* __restrict__ acc2k) {
   int G = K * bs;
+  // first kernel of a batch-step: zero the clip's per-client sum / sumsq
+  // slots (their last reader, the previous step's k_clip_sgd_mb, precedes
+  // this kernel in stream order)
+  if (blockIdx.x == 0)
+    for (int q = threadIdx.x; q < 2 * K; q += blockDim.x) acc2k[q] = 0.0;
   for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
        i < (long long)G * 784; i += (long long)gridDim.x * blockDim.x) {
     int g = (int)(i / 784), j = (int)(i % 784);
@@ -216,12 +223,28 @@ __device__ __forceinline__ void conv2_tap_offsets(int kc, int cs, int rs,
 static_assert(24 % C2F_ROWS == 0 && (C2F_ROWS * 24) % 96 == 0 &&
               C2F_CS % 4 == 0 && C2F_CS / 4 <= 64,
               "conv2 fwd slab: 6 m-tiles per block, float4 plane copies");
-__global__ __launch_bounds__(256)
-void k_conv2_fwd_mfma_mb(const float* __restrict__ a1,
-                         const float* __restrict__ w2t_stack,
-                         const float* __restrict__ params, long long P,
-                         long long ob2, int bs, int K,
-                         float* __restrict__ r2) {
+// POOL = false stores r2 (bias + ReLU).  POOL = true never writes r2: it
+// finishes with maxpool 2x2 + dropout(p1) and writes a2 / pidx / m2.  The
+// mapping of an MFMA row to an output position only enters through
+// base[i] (no output's k-chain depends on it), so POOL maps row
+// il = 4q + e of m-tile i to window element e of pool cell px = 4i + q of
+// the wave's pool row: wave mh = w >> 1 owns slab rows 2mh, 2mh + 1, and
+// the D fragment of lane (il, kc) is then acc[i][n][0..3] = the 2x2 window
+// of cell px = 4i + kc of channel co = il.. in pool_drop_cell's order
+// (base[0], base[1], base[24], base[25]): bias, ReLU and the strict->
+// argmax are in-register.  The cells then go through the (dead) staging
+// LDS so that the Philox draw runs in a rolled loop behind the
+// accumulators and consecutive lanes store consecutive cells.
+static_assert(C2F_ROWS == 4 && 2 * 64 * 24 <= 32 * C2F_CS,
+              "POOL epilogue: waves 2mh, 2mh+1 own pool row mh of the slab; "
+              "the cell image fits the staging LDS");
+template <bool POOL>
+__device__ __forceinline__ void conv2_fwd_body(
+    const float* __restrict__ a1, const float* __restrict__ w2t_stack,
+    const float* __restrict__ params, long long P, long long ob2, int bs,
+    float* __restrict__ r2, float p1, unsigned long long seed,
+    unsigned long long offset, float* __restrict__ a2,
+    unsigned char* __restrict__ pidx, unsigned char* __restrict__ m2) {
   __shared__ __attribute__((aligned(16))) float lds[32 * C2F_CS];
   long long g = blockIdx.x / C2F_SLABS;
   int sl = blockIdx.x % C2F_SLABS;
@@ -241,8 +264,13 @@ void k_conv2_fwd_mfma_mb(const float* __restrict__ a1,
   conv2_tap_offsets(kc, C2F_CS, 26, 1, off);
   #pragma unroll
   for (int i = 0; i < 3; ++i) {
-    int m = (mh * 3 + i) * 16 + il;
-    base[i] = (m / 24) * 26 + m % 24;
+    if (POOL) {
+      int q = il >> 2, e = il & 3;
+      base[i] = (2 * mh + (e >> 1)) * 26 + 2 * (4 * i + q) + (e & 1);
+    } else {
+      int m = (mh * 3 + i) * 16 + il;
+      base[i] = (m / 24) * 26 + m % 24;
+    }
   }
   const float* wp = w2t_stack + (long long)k * 18432 + kc * 64 + nh * 32 + il;
   f32x4 acc[3][2];
@@ -266,25 +294,121 @@ void k_conv2_fwd_mfma_mb(const float* __restrict__ a1,
     }
   }
   const float* b2 = params + (long long)k * P + ob2;
+  if (!POOL) {
+    #pragma unroll
+    for (int n = 0; n < 2; ++n) {
+      int co = nh * 32 + n * 16 + il;
+      float bias = b2[co];
+      #pragma unroll
+      for (int i = 0; i < 3; ++i) {
+        int om = sl * (C2F_ROWS * 24) + (mh * 3 + i) * 16 + kc * 4;
+        float4 v;
+        v.x = acc[i][n][0] + bias; v.y = acc[i][n][1] + bias;
+        v.z = acc[i][n][2] + bias; v.w = acc[i][n][3] + bias;
+        v.x = v.x > 0.f ? v.x : 0.f; v.y = v.y > 0.f ? v.y : 0.f;
+        v.z = v.z > 0.f ? v.z : 0.f; v.w = v.w > 0.f ? v.w : 0.f;
+        *reinterpret_cast<float4*>(r2 + (g * 64 + co) * 576 + om) = v;
+      }
+    }
+    return;
+  }
+  // phase 1: the block's 64 co x 24 cells (2 pool rows x 12) as max and
+  // argmax | gate << 2, in [co][24] order, over the staged a1
+  float* cmax = lds;
+  int* cidx = reinterpret_cast<int*>(lds + 64 * 24);
+  __syncthreads();
   #pragma unroll
   for (int n = 0; n < 2; ++n) {
     int co = nh * 32 + n * 16 + il;
     float bias = b2[co];
     #pragma unroll
     for (int i = 0; i < 3; ++i) {
-      int om = sl * (C2F_ROWS * 24) + (mh * 3 + i) * 16 + kc * 4;
-      float4 v;
-      v.x = acc[i][n][0] + bias; v.y = acc[i][n][1] + bias;
-      v.z = acc[i][n][2] + bias; v.w = acc[i][n][3] + bias;
-      v.x = v.x > 0.f ? v.x : 0.f; v.y = v.y > 0.f ? v.y : 0.f;
-      v.z = v.z > 0.f ? v.z : 0.f; v.w = v.w > 0.f ? v.w : 0.f;
-      *reinterpret_cast<float4*>(r2 + (g * 64 + co) * 576 + om) = v;
+      float v0 = acc[i][n][0] + bias, v1 = acc[i][n][1] + bias;
+      float v2 = acc[i][n][2] + bias, v3 = acc[i][n][3] + bias;
+      v0 = v0 > 0.f ? v0 : 0.f; v1 = v1 > 0.f ? v1 : 0.f;
+      v2 = v2 > 0.f ? v2 : 0.f; v3 = v3 > 0.f ? v3 : 0.f;
+      float m = v0; int idx = 0;
+      if (v1 > m) { m = v1; idx = 1; }
+      if (v2 > m) { m = v2; idx = 2; }
+      if (v3 > m) { m = v3; idx = 3; }
+      int c = co * 24 + mh * 12 + 4 * i + kc;
+      cmax[c] = m;
+      cidx[c] = idx | (m > 0.f ? 4 : 0);
     }
+  }
+  __syncthreads();
+  // phase 2: thread j takes cells j, j + 256, ..; the 24 cells of a co are
+  // one 96 B run of a2 (24 B of pidx / m2) at cell sl * 24 of its plane
+  float inv_keep = (p1 < 1.f) ? 1.f / (1.f - p1) : 0.f;
+  int b = (int)(g % bs);
+  #pragma unroll 1
+  for (int c = threadIdx.x; c < 64 * 24; c += 256) {
+    int co = c / 24, rem = c % 24;
+    int lc = co * 144 + sl * 24 + rem;   // cell within the image
+    long long i = g * 9216 + lc;
+    int li = b * 9216 + lc;              // client-local: the Philox key
+    float m = cmax[c];
+    unsigned char keep = 1;
+    if (p1 > 0.f) {
+      hiprandStatePhilox4_32_10_t st;
+      hiprand_init(seed, (unsigned long long)(li >> 2), offset, &st);
+      float4 u = hiprand_uniform4(&st);
+      float uu = (li & 3) == 0 ? u.x : (li & 3) == 1 ? u.y
+                 : (li & 3) == 2 ? u.z : u.w;
+      keep = uu >= p1;
+    }
+    pidx[i] = (unsigned char)cidx[c];
+    m2[i] = keep;
+    a2[i] = keep ? m * inv_keep : 0.f;
   }
 }
 
+__global__ __launch_bounds__(256)
+void k_conv2_fwd_mfma_mb(const float* __restrict__ a1,
+                         const float* __restrict__ w2t_stack,
+                         const float* __restrict__ params, long long P,
+                         long long ob2, int bs, int K,
+                         float* __restrict__ r2) {
+  conv2_fwd_body<false>(a1, w2t_stack, params, P, ob2, bs, r2, 0.f, 0ull,
+                        0ull, nullptr, nullptr, nullptr);
+}
+
+// the two metadata wrappers of the POOL form: seeds[k] from the device
+// array (mega round) or the seed as a launch argument (K = 1)
+__global__ __launch_bounds__(256)
+__attribute__((amdgpu_waves_per_eu(5, 5)))
+void k_conv2_fwd_pool_mfma_mb(const float* __restrict__ a1,
+                              const float* __restrict__ w2t_stack,
+                              const float* __restrict__ params, long long P,
+                              long long ob2, int bs, int K, float p1,
+                              const long long* __restrict__ seeds,
+                              unsigned long long offset,
+                              float* __restrict__ a2,
+                              unsigned char* __restrict__ pidx,
+                              unsigned char* __restrict__ m2) {
+  int k = (int)(blockIdx.x / C2F_SLABS / bs);
+  conv2_fwd_body<true>(a1, w2t_stack, params, P, ob2, bs, nullptr, p1,
+                       (unsigned long long)seeds[k], offset, a2, pidx, m2);
+}
+
+__global__ __launch_bounds__(256)
+__attribute__((amdgpu_waves_per_eu(5, 5)))
+void k_conv2_fwd_pool_mfma(const float* __restrict__ a1,
+                           const float* __restrict__ w2t_stack,
+                           const float* __restrict__ params, long long P,
+                           long long ob2, int bs, int K, float p1,
+                           unsigned long long seed,
+                           unsigned long long offset,
+                           float* __restrict__ a2,
+                           unsigned char* __restrict__ pidx,
+                           unsigned char* __restrict__ m2) {
+  conv2_fwd_body<true>(a1, w2t_stack, params, P, ob2, bs, nullptr, p1, seed,
+                       offset, a2, pidx, m2);
+}
+
 // maxpool 2x2 + dropout(p1) of pool cell i, whose 2x2 window starts at
-// `base`: a2 = keep ? max/(1-p1) : 0; save argmax + mask.  The Philox
+// `base`: a2 = keep ? max/(1-p1) : 0; save argmax (bits 0-1 of pidx), the
+// ReLU gate max > 0 (bit 2: all the backward needs of r2) + mask.  The Philox
 // key is (seed, li >> 2, batch offset) with li the CLIENT-LOCAL cell
 // index, so a client's masks do not depend on which driver or which
 // stack slot trains it.  Index is the wrapper's own index width (int
@@ -310,7 +434,7 @@ __device__ __forceinline__ void pool_drop_cell(
                : (li & 3) == 2 ? u.z : u.w;
     keep = uu >= p1;
   }
-  pidx[i] = (unsigned char)idx;
+  pidx[i] = (unsigned char)(idx | (m > 0.f ? 4 : 0));
   m2[i] = keep;
   a2[i] = keep ? m * inv_keep : 0.f;
 }
@@ -608,10 +732,16 @@ __global__ __launch_bounds__(FC1R_BLK) void k_fc1_fwd_reduce_mb(const float* __r
 // fc2 + softmax + CE for one sample row (one block): logits = W4 @ a3 +
 // b4 ; softmax ; *loss += -log p[target]/Bk ; dlogit = (p - onehot)/Bk,
 // Bk the row count of the client's batch.  sm holds C floats of LDS.
+// The row's dlogits also stay in sm, and the block then does the row's
+// fc2 backward-data: dz3[kk] = sum_j dlogit[j] * W4[j][kk] (j ascending),
+// gated by the fc1 dropout mask and z3 > 0.  z3r / m3r / dz3r point at the
+// row's 128 elements.
 __device__ __forceinline__ void fc2_loss_row(
     const float* __restrict__ ap, const float* __restrict__ w4,
     const float* __restrict__ b4, int target, int Bk, int C,
-    float* __restrict__ dl, float* __restrict__ loss, float* sm) {
+    float* __restrict__ dl, float* __restrict__ loss, float* sm,
+    const float* __restrict__ z3r, const unsigned char* __restrict__ m3r,
+    float p2, float* __restrict__ dz3r) {
   for (int j = threadIdx.x; j < C; j += blockDim.x) {
     const float* wp = w4 + (long long)j * 128;
     float s = b4[j];
@@ -627,11 +757,25 @@ __device__ __forceinline__ void fc2_loss_row(
     float z = 0.f;
     for (int j = 0; j < C; ++j) { sm[j] = __expf(sm[j] - mx); z += sm[j]; }
     float inv = 1.f / z;
+    float pt = sm[target] * inv;
     for (int j = 0; j < C; ++j) {
       float p = sm[j] * inv;
-      dl[j] = (p - (j == target ? 1.f : 0.f)) / (float)Bk;
+      float d = (p - (j == target ? 1.f : 0.f)) / (float)Bk;
+      dl[j] = d;
+      sm[j] = d;
     }
-    atomicAdd(loss, -__logf(fmaxf(sm[target] * inv, 1e-30f)) / (float)Bk);
+    atomicAdd(loss, -__logf(fmaxf(pt, 1e-30f)) / (float)Bk);
+  }
+  __syncthreads();
+  if (threadIdx.x < 128) {
+    int kk = threadIdx.x;
+    float zv = z3r[kk];
+    unsigned char mk = m3r[kk];
+    float s = 0.f;
+    for (int j = 0; j < C; ++j)
+      s = fmaf(sm[j], w4[(long long)j * 128 + kk], s);
+    float gg = (p2 > 0.f) ? (mk ? s * (1.f / (1.f - p2)) : 0.f) : s;
+    dz3r[kk] = zv > 0.f ? gg : 0.f;
   }
 }
 
@@ -640,14 +784,20 @@ __global__ void k_fc2_loss_fwd(const float* __restrict__ a3,
                                const float* __restrict__ b4,
                                const int* __restrict__ yb, int B, int C,
                                float* __restrict__ dlogits,
-                               float* __restrict__ loss_acc) {
+                               float* __restrict__ loss_acc,
+                               const float* __restrict__ z3,
+                               const unsigned char* __restrict__ m3,
+                               float p2, float* __restrict__ dz3) {
   extern __shared__ float sm[];
   int b = blockIdx.x;
   fc2_loss_row(a3 + (long long)b * 128, w4, b4, yb[b], B, C,
-               dlogits + (long long)b * C, loss_acc, sm);
+               dlogits + (long long)b * C, loss_acc, sm,
+               z3 + (long long)b * 128, m3 + (long long)b * 128, p2,
+               dz3 + (long long)b * 128);
 }
 
-// one block per super-row g; yb<0 (inactive) rows zero their dlogits
+// one block per super-row g; yb<0 (inactive) rows zero their dlogits and
+// their dz3 (what backward-data gives from zero dlogits)
 __global__ void k_fc2_loss_fwd_mb(const float* __restrict__ a3,
                                   const float* __restrict__ params,
                                   long long P, long long ow4, long long ob4,
@@ -655,7 +805,10 @@ __global__ void k_fc2_loss_fwd_mb(const float* __restrict__ a3,
                                   int t, int bs, int K, int C,
                                   const int* __restrict__ yb,
                                   float* __restrict__ dlogits,
-                                  float* __restrict__ loss_out) {
+                                  float* __restrict__ loss_out,
+                                  const float* __restrict__ z3,
+                                  const unsigned char* __restrict__ m3,
+                                  float p2, float* __restrict__ dz3) {
   extern __shared__ float sm[];
   long long g = blockIdx.x;
   int k = (int)(g / bs);
@@ -663,12 +816,13 @@ __global__ void k_fc2_loss_fwd_mb(const float* __restrict__ a3,
   if (target < 0) {
     for (int j = threadIdx.x; j < C; j += blockDim.x)
       dlogits[g * C + j] = 0.f;
+    if (threadIdx.x < 128) dz3[g * 128 + threadIdx.x] = 0.f;
     return;
   }
   fc2_loss_row(a3 + g * 128, params + (long long)k * P + ow4,
                params + (long long)k * P + ob4, target,
                mega_Bk(counts, k, t, bs), C, dlogits + g * C, loss_out + k,
-               sm);
+               sm, z3 + g * 128, m3 + g * 128, p2, dz3 + g * 128);
 }
 
 // fc2 backward (weights): grid = K * ceil(C*128/256)
@@ -692,29 +846,6 @@ __global__ void k_fc2_bwd_w_mb(const float* __restrict__ dlogits,
   }
   grads[(long long)k * P + ow4 + i0] = s;
   if (kk == 0) grads[(long long)k * P + ob4 + j] = sb;
-}
-
-__global__ void k_fc2_bwd_x_mb(const float* __restrict__ dlogits,
-                               const float* __restrict__ params, long long P,
-                               long long ow4, const float* __restrict__ z3,
-                               const unsigned char* __restrict__ m3, int bs,
-                               int K, int C, float p2,
-                               float* __restrict__ dz3) {
-  long long total = (long long)K * bs * 128;
-  float inv_keep = 1.f / (1.f - p2);
-  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
-       i < total; i += (long long)gridDim.x * blockDim.x) {
-    int kk = (int)(i % 128);
-    long long g = i / 128;
-    int k = (int)(g / bs);
-    const float* w4 = params + (long long)k * P + ow4;
-    const float* dl = dlogits + g * C;
-    float s = 0.f;
-    for (int j = 0; j < C; ++j)
-      s = fmaf(dl[j], w4[(long long)j * 128 + kk], s);
-    float gg = (p2 > 0.f) ? (m3[i] ? s * inv_keep : 0.f) : s;
-    dz3[i] = z3[i] > 0.f ? gg : 0.f;
-  }
 }
 
 // Column map of the two fc1 backward kernels.  n = 9216 is an OUTPUT
@@ -880,28 +1011,80 @@ void k_fc1_bwd_x_mfma_mb(const float* __restrict__ dz3,
   else fc1_bwd_x_body<1>(dz, w3, da, bs, col0);
 }
 
-__global__ void k_pool_drop_bwd_mb(const float* __restrict__ da2,
-                                   const unsigned char* __restrict__ pidx,
-                                   const unsigned char* __restrict__ m2,
-                                   const float* __restrict__ r2, int bs,
-                                   int K, float p1,
-                                   float* __restrict__ dz2) {
-  long long total = (long long)K * bs * 9216;
+// the conv2 bias sum of one (client, channel) block: every thread's
+// partial s through the 64-lane shuffle-down tree, then the wave sums in
+// wave order
+__device__ __forceinline__ void conv2_bias_block_sum(float s,
+                                                     float* __restrict__ out) {
+  for (int d = 32; d > 0; d >>= 1) s += __shfl_down(s, d, 64);
+  __shared__ float lds[4];
+  if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float tt = 0.f;
+    for (int q = 0; q < (int)blockDim.x / 64; ++q) tt += lds[q];
+    *out = tt;
+  }
+}
+
+// dropout(p1) + maxpool 2x2 + ReLU backward, and the conv2 bias gradient
+// of the dz2 it writes.  grid = K * 64, FBLK threads, one block per
+// (client, co).  Thread t walks the client's bs * 576 elements of that
+// channel e = t, t + 256, .. (b = e / 576, o = e % 576): the element is
+// its cell's gradient gg iff pidx names it AND carries the gate bit
+// (pidx == d | 4, the forward's max > 0), else 0.  It reads no r2.  Each
+// element is stored to dz2 (coalesced dwords) and added to the thread's
+// partial in e order, exactly the chain k_conv2_bwd_b_mb runs over a
+// stored dz2.  PDB_U elements are loaded before the first add; past the
+// end a clamped (valid) element is loaded and dropped by selects, so no
+// load sits behind a branch.
+#define PDB_U 9  /* 45 strides at bs = 20: five groups of 27 loads */
+__global__ __launch_bounds__(FBLK)
+void k_pool_drop_bwd_bias_mb(const float* __restrict__ da2,
+                             const unsigned char* __restrict__ pidx,
+                             const unsigned char* __restrict__ m2, int bs,
+                             int K, float p1, float* __restrict__ dz2,
+                             float* __restrict__ grads, long long P,
+                             long long ob2) {
+  int k = blockIdx.x / 64;
+  int co = blockIdx.x % 64;
+  int n = bs * 576;
+  bool drop = p1 > 0.f;
   float inv_keep = (p1 < 1.f) ? 1.f / (1.f - p1) : 0.f;
-  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
-       i < total; i += (long long)gridDim.x * blockDim.x) {
-    int px = (int)(i % 12), py = (int)((i / 12) % 12);
-    int c = (int)((i / 144) % 64);
-    long long g = i / 9216;
-    float gg = (p1 > 0.f) ? (m2[i] ? da2[i] * inv_keep : 0.f) : da2[i];
-    int idx = pidx[i];
-    long long base = ((g * 64 + c) * 24 + 2 * py) * 24 + 2 * px;
+  float sc = drop ? inv_keep : 1.f;
+  const long long row0 = (long long)k * bs * 64 + co;  // plane of b = 0
+  float s = 0.f;
+  for (int e0 = threadIdx.x; e0 < n; e0 += PDB_U * FBLK) {
+    float da[PDB_U];
+    unsigned char pi[PDB_U], mk[PDB_U];
     #pragma unroll
-    for (int d = 0; d < 4; ++d) {
-      long long o = base + (d >> 1) * 24 + (d & 1);
-      dz2[o] = (d == idx && r2[o] > 0.f) ? gg : 0.f;
+    for (int u = 0; u < PDB_U; ++u) {
+      int e = e0 + u * FBLK;
+      e = e < n ? e : n - 1;
+      int b = e / 576, o = e % 576;
+      int y = o / 24, x = o % 24;
+      long long cell = (row0 + (long long)b * 64) * 144 + (y >> 1) * 12
+                       + (x >> 1);
+      da[u] = da2[cell];
+      pi[u] = pidx[cell];
+      mk[u] = m2[cell];
+    }
+    #pragma unroll
+    for (int u = 0; u < PDB_U; ++u) {
+      int e = e0 + u * FBLK;
+      int ec = e < n ? e : n - 1;
+      int b = ec / 576, o = ec % 576;
+      int d = ((o / 24) & 1) * 2 + (o & 1);  // 24 is even: x & 1 == o & 1
+      // = drop ? (mk ? da * inv_keep : 0) : da, as selects (da * 1.f == da)
+      float gg = (drop && !mk[u]) ? 0.f : da[u] * sc;
+      float v = pi[u] == (d | 4) ? gg : 0.f;
+      if (e < n) {
+        dz2[(row0 + (long long)b * 64) * 576 + o] = v;
+        s += v;
+      }
     }
   }
+  conv2_bias_block_sum(s, grads + (long long)k * P + ob2 + co);
 }
 
 // conv2 backward weights (f32 MFMA): per image, dw[co][n] = sum over the
@@ -1038,6 +1221,9 @@ __global__ void k_conv2_bwd_w_fold_mb(const float* __restrict__ slab,
   grads[(long long)k * P + ow2 + i] = s;
 }
 
+// bias sum over a dz2 that is already in memory: the per-kernel debug
+// launchers only (they take dz2 as an input).  The drivers get the same
+// chain from k_pool_drop_bwd_bias_mb, which writes dz2.
 __global__ void k_conv2_bwd_b_mb(const float* __restrict__ dz2,
                                  float* __restrict__ grads, long long P,
                                  long long ob2, int bs, int K) {
@@ -1049,15 +1235,7 @@ __global__ void k_conv2_bwd_b_mb(const float* __restrict__ dz2,
     int o = t % 576, b = t / 576;
     s += dzk[((long long)b * 64 + co) * 576 + o];
   }
-  for (int d = 32; d > 0; d >>= 1) s += __shfl_down(s, d, 64);
-  __shared__ float lds[4];
-  if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float tt = 0.f;
-    for (int q = 0; q < (int)blockDim.x / 64; ++q) tt += lds[q];
-    grads[(long long)k * P + ob2 + co] = tt;
-  }
+  conv2_bias_block_sum(s, grads + (long long)k * P + ob2 + co);
 }
 
 // conv2 backward data (f32 MFMA), implicit GEMM from a zero-padded dz2.
@@ -1211,8 +1389,9 @@ __global__ void k_conv1_bwd_w_mb(const float* __restrict__ x,
 
 // per-client clip + sufficient stats + SGD over the gradient stacks.
 // Stage 1: per-(k, chunk) partial sum/sumsq -> f64 atomics into acc[2k]
-// (few hundred atomics per client per step).  Stage 2: per-client scale
-// + stats accumulate + SGD in one elementwise pass.
+// (few hundred atomics per client per step).  Stage 2 (k_clip_sgd_mb):
+// per-client scale + SGD in one elementwise pass, whose block 0 also
+// accumulates the K clients' clipped stats.
 // one block per (client, contiguous chunk): block-local tree reduce,
 // ONE f64 atomicAdd pair per block (~K * ceil(P/65536) atomics per step)
 #define SUMSQ_CHUNK 32768
@@ -1285,6 +1464,14 @@ __global__ void k_clip_sgd_mb(float* __restrict__ params,
                               float* __restrict__ stats_out) {
   long long total = (long long)K * P;
   float lr = lr_t[0];
+  // block 0 also accumulates the per-client clipped stats:
+  // stats_out[2k] += scale * sum, stats_out[2k+1] += scale^2 * sumsq
+  if (blockIdx.x == 0)
+    for (int k = threadIdx.x; k < K; k += blockDim.x) {
+      float scale = clip_scale(acc, k, max_norm, eps);
+      stats_out[2 * k] += scale * (float)acc[2 * k];
+      stats_out[2 * k + 1] += scale * scale * (float)acc[2 * k + 1];
+    }
   long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
   if (i >= total) return;
   int k = (int)(i / P);
@@ -1300,20 +1487,6 @@ __global__ void k_clip_sgd_mb(float* __restrict__ params,
     if constexpr (STORE_G) grads[i] = gv;
     params[i] -= lr * gv;
   }
-}
-
-// per-client clipped-stats accumulate: stats_out[2k] += scale*sum,
-// stats_out[2k+1] += scale^2*sumsq (one thread per client)
-__global__ void k_stats_mb(const double* __restrict__ acc, int K,
-                           float max_norm, float eps,
-                           float* __restrict__ stats_out) {
-  int k = blockIdx.x * blockDim.x + threadIdx.x;
-  if (k >= K) return;
-  float norm = (float)sqrt(acc[2 * k + 1]);
-  float scale = (max_norm > 0.f && norm > max_norm)
-                    ? max_norm / (norm + eps) : 1.f;
-  stats_out[2 * k] += scale * (float)acc[2 * k];
-  stats_out[2 * k + 1] += scale * scale * (float)acc[2 * k + 1];
 }
 
 // weighted pseudo-gradients + deterministic accumulate into round_accum
@@ -1665,19 +1838,22 @@ extern "C" void launch_cnn_epoch(
       EPOCH_CHK("k_w2rotbf_mb");
       hipLaunchKernelGGL(k_conv2_fwd_mfma_mb_bf16, dim3(B * 9), dim3(FBLK),
                          0, s, ws.a1, params, P, o.w2, o.b2, B, K, ws.r2);
+      EPOCH_CHK("k_conv2_fwd_mfma_mb_bf16");
+      hipLaunchKernelGGL(k_pool_drop_fwd, dim3((B * 9216 + FBLK - 1) / FBLK),
+                         dim3(FBLK), 0, s, ws.r2, B, p1, seed, off, ws.a2,
+                         ws.pidx, ws.m2);
+      EPOCH_CHK("k_pool_drop_fwd");
     } else {
       hipLaunchKernelGGL(k_w2_layouts_mb, dim3((18432 + FBLK - 1) / FBLK),
                          dim3(FBLK), 0, s, params, P, o.w2, K, ws.w2t,
                          ws.w2rot);
       EPOCH_CHK("k_w2_layouts_mb");
-      hipLaunchKernelGGL(k_conv2_fwd_mfma_mb, dim3(B * C2F_SLABS),
-                         dim3(FBLK), 0, s, ws.a1, ws.w2t, params, P, o.b2, B, K, ws.r2);
+      // conv2 + pool + dropout in one kernel: no r2 on the fp32 path
+      hipLaunchKernelGGL(k_conv2_fwd_pool_mfma, dim3(B * C2F_SLABS),
+                         dim3(FBLK), 0, s, ws.a1, ws.w2t, params, P, o.b2, B,
+                         K, p1, seed, off, ws.a2, ws.pidx, ws.m2);
+      EPOCH_CHK("k_conv2_fwd_pool_mfma");
     }
-    EPOCH_CHK("k_conv2_fwd_mfma_mb");
-    hipLaunchKernelGGL(k_pool_drop_fwd, dim3((B * 9216 + FBLK - 1) / FBLK),
-                       dim3(FBLK), 0, s, ws.r2, B, p1, seed, off, ws.a2,
-                       ws.pidx, ws.m2);
-    EPOCH_CHK("k_pool_drop_fwd");
     if (use_bf16) {
       hipLaunchKernelGGL(k_fc1_fwd_mfma_mb_bf16, dim3(FC1B_SPLIT), dim3(FBLK),
                          0, s, ws.a2, params, P, o.w3, B, K, ws.wsl);
@@ -1698,16 +1874,13 @@ extern "C" void launch_cnn_epoch(
     EPOCH_CHK("k_fc1_fwd_reduce");
     hipLaunchKernelGGL(k_fc2_loss_fwd, dim3(B), dim3(FBLK),
                        C * (int)sizeof(float), s, ws.a3, params + o.w4,
-                       params + o.b4, ws.yb, B, C, ws.dlogits, loss_acc);
+                       params + o.b4, ws.yb, B, C, ws.dlogits, loss_acc,
+                       ws.z3, ws.m3, p2, ws.dz3);
     EPOCH_CHK("k_fc2_loss_fwd");
     hipLaunchKernelGGL(k_fc2_bwd_w_mb, dim3((C * 128 + FBLK - 1) / FBLK),
                        dim3(FBLK), 0, s, ws.dlogits, ws.a3, grads, P, o.w4,
                        o.b4, B, K, C);
     EPOCH_CHK("k_fc2_bwd_w_mb");
-    hipLaunchKernelGGL(k_fc2_bwd_x_mb, dim3((B * 128 + FBLK - 1) / FBLK),
-                       dim3(FBLK), 0, s, ws.dlogits, params, P, o.w4, ws.z3,
-                       ws.m3, B, K, C, p2, ws.dz3);
-    EPOCH_CHK("k_fc2_bwd_x_mb");
     hipLaunchKernelGGL(k_fc1_bwd_w_mfma_mb, dim3(144), dim3(FBLK), 0, s,
                        ws.dz3, ws.a2, grads, P, o.w3, grads, P, o.b3, B, K);
     EPOCH_CHK("k_fc1_bwd_w_mfma_mb");
@@ -1715,10 +1888,10 @@ extern "C" void launch_cnn_epoch(
                        dim3(64 * FC1X_WAVES), 0, s,
                        ws.dz3, params, P, o.w3, B, K, ws.da2);
     EPOCH_CHK("k_fc1_bwd_x_mfma_mb");
-    hipLaunchKernelGGL(k_pool_drop_bwd_mb, dim3((B * 9216 + FBLK - 1) / FBLK),
-                       dim3(FBLK), 0, s, ws.da2, ws.pidx, ws.m2, ws.r2, B, K,
-                       p1, ws.dz2);
-    EPOCH_CHK("k_pool_drop_bwd_mb");
+    hipLaunchKernelGGL(k_pool_drop_bwd_bias_mb, dim3(64), dim3(FBLK), 0, s,
+                       ws.da2, ws.pidx, ws.m2, B, K, p1, ws.dz2, grads, P,
+                       o.b2);
+    EPOCH_CHK("k_pool_drop_bwd_bias_mb");
     if (use_bf16) {
       hipLaunchKernelGGL(k_conv2_bwd_w_mfma_mb_bf16, dim3(18 * B), dim3(FBLK),
                          0, s, ws.dz2, ws.a1, B, K, ws.wsl);
@@ -1730,9 +1903,6 @@ extern "C" void launch_cnn_epoch(
     hipLaunchKernelGGL(k_conv2_bwd_w_fold_mb, dim3((18432 + FBLK - 1) / FBLK),
                        dim3(FBLK), 0, s, ws.wsl, grads, P, o.w2, B, K);
     EPOCH_CHK("k_conv2_bwd_w_fold_mb");
-    hipLaunchKernelGGL(k_conv2_bwd_b_mb, dim3(64), dim3(FBLK), 0, s,
-                       ws.dz2, grads, P, o.b2, B, K);
-    EPOCH_CHK("k_conv2_bwd_b_mb");
     if (use_bf16)
       hipLaunchKernelGGL(k_conv2_bwd_x_mfma_mb_bf16, dim3(B * 22), dim3(FBLK),
                          0, s, ws.dz2,
@@ -1828,7 +1998,7 @@ extern "C" void launch_cnn_round_mega(
     hipLaunchKernelGGL(k_gather_mb, dim3((G * 784 + FBLK - 1) / FBLK),
                        dim3(FBLK), 0, s, shard_x, shard_y, orders_dev,
                        row_bases_dev, order_offs_dev, counts_dev, t, bs, K,
-                       xb, yb);
+                       xb, yb, acc2k);
     hipLaunchKernelGGL(k_conv1_fwd_mb,
                        dim3((int)(((long long)G * 21632 + FBLK - 1) / FBLK)),
                        dim3(FBLK), 0, s, xb, params_stack, P, o.w1, o.b1,
@@ -1840,18 +2010,20 @@ extern "C" void launch_cnn_round_mega(
                          reinterpret_cast<__bf16*>(w2rot_stack));
       hipLaunchKernelGGL(k_conv2_fwd_mfma_mb_bf16, dim3(G * 9), dim3(FBLK),
                          0, s, a1, params_stack, P, o.w2, o.b2, bs, K, r2);
+      hipLaunchKernelGGL(k_pool_drop_fwd_mb,
+                         dim3((int)(((long long)G * 9216 + FBLK - 1) / FBLK)),
+                         dim3(FBLK), 0, s, r2, bs, K, p1, seeds_dev, off,
+                         a2, pidx, m2);
     } else {
       hipLaunchKernelGGL(k_w2_layouts_mb,
                          dim3((int)(((long long)K * 18432 + FBLK - 1) / FBLK)),
                          dim3(FBLK), 0, s, params_stack, P, o.w2, K,
                          w2t_stack, w2rot_stack);
-      hipLaunchKernelGGL(k_conv2_fwd_mfma_mb, dim3(G * C2F_SLABS),
-                         dim3(FBLK), 0, s, a1, w2t_stack, params_stack, P, o.b2, bs, K, r2);
+      // conv2 + pool + dropout in one kernel: no r2 on the fp32 path
+      hipLaunchKernelGGL(k_conv2_fwd_pool_mfma_mb, dim3(G * C2F_SLABS),
+                         dim3(FBLK), 0, s, a1, w2t_stack, params_stack, P,
+                         o.b2, bs, K, p1, seeds_dev, off, a2, pidx, m2);
     }
-    hipLaunchKernelGGL(k_pool_drop_fwd_mb,
-                       dim3((int)(((long long)G * 9216 + FBLK - 1) / FBLK)),
-                       dim3(FBLK), 0, s, r2, bs, K, p1, seeds_dev, off,
-                       a2, pidx, m2);
     if (use_bf16) {
       hipLaunchKernelGGL(k_fc1_fwd_mfma_mb_bf16, dim3(K * 36), dim3(FBLK),
                          0, s, a2, params_stack, P, o.w3, bs, K, slab);
@@ -1871,23 +2043,20 @@ extern "C" void launch_cnn_round_mega(
     }
     hipLaunchKernelGGL(k_fc2_loss_fwd_mb, dim3(G), dim3(FBLK),
                        C * (int)sizeof(float), s, a3, params_stack, P, o.w4,
-                       o.b4, counts_dev, t, bs, K, C, yb, dlogits, loss_out);
+                       o.b4, counts_dev, t, bs, K, C, yb, dlogits, loss_out,
+                       z3, m3, p2, dz3);
     int perk_fc2 = (C * 128 + FBLK - 1) / FBLK;
     hipLaunchKernelGGL(k_fc2_bwd_w_mb, dim3(K * perk_fc2), dim3(FBLK), 0, s,
                        dlogits, a3, grads_stack, P, o.w4, o.b4, bs, K, C);
-    hipLaunchKernelGGL(k_fc2_bwd_x_mb,
-                       dim3((int)(((long long)G * 128 + FBLK - 1) / FBLK)),
-                       dim3(FBLK), 0, s, dlogits, params_stack, P, o.w4,
-                       z3, m3, bs, K, C, p2, dz3);
     hipLaunchKernelGGL(k_fc1_bwd_w_mfma_mb, dim3(K * 144), dim3(FBLK), 0, s,
                        dz3, a2, grads_stack, P, o.w3, grads_stack, P, o.b3,
                        bs, K);
     hipLaunchKernelGGL(k_fc1_bwd_x_mfma_mb, dim3(K * FC1X_BLKS),
                        dim3(64 * FC1X_WAVES), 0, s,
                        dz3, params_stack, P, o.w3, bs, K, da2);
-    hipLaunchKernelGGL(k_pool_drop_bwd_mb,
-                       dim3((int)(((long long)G * 9216 + FBLK - 1) / FBLK)),
-                       dim3(FBLK), 0, s, da2, pidx, m2, r2, bs, K, p1, dz2);
+    hipLaunchKernelGGL(k_pool_drop_bwd_bias_mb, dim3(K * 64), dim3(FBLK), 0,
+                       s, da2, pidx, m2, bs, K, p1, dz2, grads_stack, P,
+                       o.b2);
     if (use_bf16) {
       hipLaunchKernelGGL(k_conv2_bwd_w_mfma_mb_bf16, dim3(18 * G), dim3(FBLK),
                          0, s, dz2, a1, bs, K, slab);
@@ -1898,8 +2067,6 @@ extern "C" void launch_cnn_round_mega(
     int perk_fold = (18432 + FBLK - 1) / FBLK;
     hipLaunchKernelGGL(k_conv2_bwd_w_fold_mb, dim3(K * perk_fold),
                        dim3(FBLK), 0, s, slab, grads_stack, P, o.w2, bs, K);
-    hipLaunchKernelGGL(k_conv2_bwd_b_mb, dim3(K * 64), dim3(FBLK), 0, s,
-                       dz2, grads_stack, P, o.b2, bs, K);
     if (use_bf16)
       hipLaunchKernelGGL(k_conv2_bwd_x_mfma_mb_bf16, dim3(G * 22), dim3(FBLK),
                          0, s, dz2,
@@ -1910,12 +2077,10 @@ extern "C" void launch_cnn_round_mega(
                          dim3(FBLK), 0, s, dz2, w2rot_stack, a1, bs, K, dz1);
     hipLaunchKernelGGL(k_conv1_bwd_w_mb, dim3(K * 32), dim3(1024), 0, s,
                        xb, dz1, grads_stack, P, o.w1, o.b1, bs, K);
-    hipMemsetAsync(acc2k, 0, 2 * K * sizeof(double), s);
+    // acc2k was zeroed by this step's k_gather_mb
     int blocks_per_k = (int)((P + SUMSQ_CHUNK - 1) / SUMSQ_CHUNK);
     hipLaunchKernelGGL(k_sumsq_mb, dim3(K * blocks_per_k), dim3(FBLK), 0, s,
                        grads_stack, P, blocks_per_k, acc2k);
-    hipLaunchKernelGGL(k_stats_mb, dim3((K + 63) / 64), dim3(64), 0, s,
-                       acc2k, K, max_norm, 1e-6f, stats_out);
     hipLaunchKernelGGL(k_clip_sgd_mb<false>, dim3(gkp), dim3(FBLK), 0, s,
                        params_stack, grads_stack, P, K, acc2k, max_norm,
                        1e-6f, lr_t, stats_out);
@@ -1941,8 +2106,6 @@ extern "C" void launch_mega_clip_sgd(float* params_stack, float* grads_stack,
   int blocks_per_k = (int)((P + SUMSQ_CHUNK - 1) / SUMSQ_CHUNK);
   hipLaunchKernelGGL(k_sumsq_mb, dim3(K * blocks_per_k), dim3(FBLK), 0, s,
                      grads_stack, P, blocks_per_k, acc2k);
-  hipLaunchKernelGGL(k_stats_mb, dim3((K + 63) / 64), dim3(64), 0, s,
-                     acc2k, K, max_norm, 1e-6f, stats_out);
   long long kp = (long long)K * P;
   int gkp = (int)((kp + FBLK - 1) / FBLK); if (gkp > 4096) gkp = 4096;
   hipLaunchKernelGGL(k_clip_sgd_mb<true>, dim3(gkp), dim3(FBLK), 0, s,
@@ -1985,6 +2148,23 @@ void launch_conv2_fwd_mfma(const float* a1, const float* w2t, const float* b2,
                            int bs, int K, float* r2, hipStream_t s) {
   hipLaunchKernelGGL(k_conv2_fwd_mfma_mb, dim3(K * bs * C2F_SLABS),
                      dim3(FBLK), 0, s, a1, w2t, b2, 64LL, 0LL, bs, K, r2);
+}
+void launch_conv2_fwd_pool_mfma(const float* a1, const float* w2t,
+                                const float* b2, int bs, int K, float p1,
+                                const long long* seeds_dev,
+                                unsigned long long offset, float* a2,
+                                unsigned char* pidx, unsigned char* m2,
+                                hipStream_t s) {
+  hipLaunchKernelGGL(k_conv2_fwd_pool_mfma_mb, dim3(K * bs * C2F_SLABS),
+                     dim3(FBLK), 0, s, a1, w2t, b2, 64LL, 0LL, bs, K, p1,
+                     seeds_dev, offset, a2, pidx, m2);
+}
+void launch_pool_drop_bwd_bias(const float* da2, const unsigned char* pidx,
+                               const unsigned char* m2, int bs, int K,
+                               float p1, float* dz2, float* db2,
+                               hipStream_t s) {
+  hipLaunchKernelGGL(k_pool_drop_bwd_bias_mb, dim3(K * 64), dim3(FBLK), 0, s,
+                     da2, pidx, m2, bs, K, p1, dz2, db2, 64LL, 0LL);
 }
 void launch_conv2_bwd_x_mfma(const float* dz2, const float* w2rot,
                              const float* a1, int bs, int K, float* dz1,

@@ -166,6 +166,20 @@ void launch_w2_layouts(const float* w2, int K, float* w2t, float* w2rot,
 void launch_conv2_fwd_mfma(const float* a1, const float* w2t,
                            const float* b2, int bs, int K, float* r2,
                            hipStream_t s);
+// the same GEMM with the maxpool + dropout(p1) epilogue: writes a2, pidx
+// (argmax | gate << 2) and m2 instead of r2; client k draws from
+// seeds_dev[k] (device array)
+void launch_conv2_fwd_pool_mfma(const float* a1, const float* w2t,
+                                const float* b2, int bs, int K, float p1,
+                                const long long* seeds_dev,
+                                unsigned long long offset, float* a2,
+                                unsigned char* pidx, unsigned char* m2,
+                                hipStream_t s);
+// dropout + maxpool + ReLU backward: dz2 and the conv2 bias sums db2[K*64]
+void launch_pool_drop_bwd_bias(const float* da2, const unsigned char* pidx,
+                               const unsigned char* m2, int bs, int K,
+                               float p1, float* dz2, float* db2,
+                               hipStream_t s);
 void launch_conv2_bwd_x_mfma(const float* dz2, const float* w2rot,
                              const float* a1, int bs, int K, float* dz1,
                              hipStream_t s);
