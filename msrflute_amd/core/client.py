@@ -599,11 +599,14 @@ class ClientPool:
         prim = self.executors[0]
         cc = prim.client_config
         data_cfg = cc["data_config"]["train"]
-        if not _fused_round_eligible(prim, data_cfg):
+        pm = prim.config.get("privacy_metrics_config", None)
+        mu = fused_round_mu(prim.config["strategy"], cc, prim.model_config,
+                            bool(pm and pm["apply_metrics"]))
+        if mu is None:
             return None
         out = self._try_graphed_mega("_mega_lstm", True, _build_mega_lstm,
                                      data_cfg, client_ids, initial_lr, seeds,
-                                     precisions=("bf16",))
+                                     precisions=("bf16",), mu=mu)
         if out is None:
             # OPT-IN: measured SLOWER than the per-client epoch-graph path
             # on ROCm 7.2 — MIOpen decomposes groups=K convs into K
@@ -614,7 +617,8 @@ class ClientPool:
             # ROCm release makes grouped conv competitive.
             out = self._try_graphed_mega(
                 "_mega_resnet", cc.get("use_mega_round_resnet", False),
-                _build_mega_resnet, data_cfg, client_ids, initial_lr, seeds)
+                _build_mega_resnet, data_cfg, client_ids, initial_lr, seeds,
+                mu=mu)
         if out is not None:
             return out
         fc = prim.fused_cnn
@@ -637,7 +641,7 @@ class ClientPool:
                 from ..ops.fused_cnn import MegaRound
                 self._mega = MegaRound(prim.arena, fc.C, fc.bs, fc.p1, fc.p2,
                                        data_cfg.get("max_grad_norm"),
-                                       use_bf16=fc.use_bf16)
+                                       use_bf16=fc.use_bf16, mu=mu)
             if self._mega.supports(len(client_ids)):
                 out = self._mega.run(store, ds, client_ids, seeds, initial_lr,
                                      self.server_arena, self.round_accums[0],
@@ -665,15 +669,15 @@ class ClientPool:
                 plan = plan_round(store, ds.user_list, chunk, schunk, dms)
                 outputs.extend(_fused_round_impl(
                     ex, store, plan, chunk, schunk, initial_lr,
-                    self.round_accums[k]))
+                    self.round_accums[k], mu))
             self._streams_dirty = True
         return outputs
 
     def _try_graphed_mega(self, attr, enabled, build, data_cfg, client_ids,
-                          initial_lr, seeds, precisions=()):
+                          initial_lr, seeds, precisions=(), mu=0.0):
         """One graph-captured cross-client round
         (ops/mega_round.GraphedMegaRound) when the model being trained is
-        the one ``build(prim, data_cfg)`` recognises (it returns the
+        the one ``build(prim, data_cfg, mu)`` recognises (it returns the
         driver, or None for any other model); the driver is kept in
         ``self.<attr>``.  ``precisions`` lists the ``mixed_precision``
         values the driver implements besides fp32.  Returns outputs or
@@ -695,7 +699,7 @@ class ClientPool:
                 or opt_cfg.get("nesterov", False)):
             return None
         if getattr(self, attr) is None:
-            mega = build(prim, data_cfg) if ops.HAS_EXT else None
+            mega = build(prim, data_cfg, mu) if ops.HAS_EXT else None
             setattr(self, attr, mega or False)
         mega = getattr(self, attr)
         if mega is False or not mega.supports(len(client_ids)):
@@ -718,7 +722,7 @@ class ClientPool:
         prim.perf_acc["clients"] = prim.perf_acc.get("clients", 0) + n_clients
 
 
-def _build_mega_lstm(prim, data_cfg):
+def _build_mega_lstm(prim, data_cfg, mu=0.0):
     """The Shakespeare char-LSTM mega round (ops/mega_shakespeare.py), or
     None if ``prim`` trains another model."""
     from ..ops.mega_shakespeare import ShakespeareMegaRound, matches_char_lstm
@@ -727,10 +731,11 @@ def _build_mega_lstm(prim, data_cfg):
     return ShakespeareMegaRound(
         prim.arena, data_cfg.get("batch_size", 4),
         data_cfg.get("max_grad_norm"),
-        use_bf16=prim.client_config.get("mixed_precision", "") == "bf16")
+        use_bf16=prim.client_config.get("mixed_precision", "") == "bf16",
+        mu=mu)
 
 
-def _build_mega_resnet(prim, data_cfg):
+def _build_mega_resnet(prim, data_cfg, mu=0.0):
     """The fed-CIFAR100 ResNet-18 mega round (ops/mega_resnet.py), or None
     if ``prim`` trains another model (or one without GroupNorm)."""
     from ..ops.mega_resnet import ResNetMegaRound, matches_resnet18
@@ -738,26 +743,39 @@ def _build_mega_resnet(prim, data_cfg):
     if cpg <= 0 or matches_resnet18(prim.arena) is None:
         return None
     return ResNetMegaRound(prim.arena, data_cfg.get("batch_size", 20),
-                           data_cfg.get("max_grad_norm"), cpg)
+                           data_cfg.get("max_grad_norm"), cpg, mu=mu)
 
 
-def _fused_round_eligible(ex, data_cfg):
-    """The fused whole-round driver trains full shards with plain SGD and
-    aggregates every layer's gradient; fall back to the per-client path
-    whenever the eager path would behave differently: a frozen layer
-    (its pseudo-grad segment must be zeroed, fedavg.py:58) or a
-    num_skips_threshold (clients can be zero-weighted mid-epoch).
-    desired_max_samples is checked per client against shard sizes by
-    lookup_round (the eager path truncates each client's epoch there)."""
-    if ex.model_config.get("freeze_layer", None):
-        return False
-    if int(ex.client_config.get("num_skips_threshold", -1)) >= 0:
-        return False
-    return True
+def fused_round_mu(strategy, client_config, model_config=None,
+                   apply_privacy_metrics=False):
+    """THE gate of the whole-round drivers (pure: config in, decision
+    out).  Returns None when the round must take the per-client path,
+    else the proximal coefficient the drivers train with: 0.0 for FedAvg,
+    ``client_config["mu"]`` (default 0.001, as in ``process_round``) for
+    FedProx.
+
+    The drivers train full shards with SGD (plus FedProx's exact
+    per-batch proximal term) and aggregate every layer's gradient with
+    weights = sample counts; fall back whenever the eager path would
+    behave differently: another strategy (DGA, FedLabels), privacy
+    metrics, a frozen layer (its pseudo-grad segment must be zeroed,
+    fedavg.py:58) or a num_skips_threshold (clients can be zero-weighted
+    mid-epoch).  desired_max_samples is checked per client against shard
+    sizes by lookup_round (the eager path truncates each client's epoch
+    there)."""
+    if strategy not in ("FedAvg", "FedProx") or apply_privacy_metrics:
+        return None
+    if (model_config or {}).get("freeze_layer", None):
+        return None
+    if int(client_config.get("num_skips_threshold", -1)) >= 0:
+        return None
+    if strategy == "FedAvg":
+        return 0.0
+    return float(client_config.get("mu", 0.001))
 
 
 def _fused_round_impl(ex, store, plan, client_ids, seeds, initial_lr,
-                      round_accum):
+                      round_accum, mu=0.0):
     """One _C.cnn_round call training ``client_ids`` on ``ex`` as planned
     (plan_round): copy-in, fused epoch, weighted pseudo-grad, accumulate
     into ``round_accum``.  Returns the per-client outputs."""
@@ -796,7 +814,7 @@ def _fused_round_impl(ex, store, plan, client_ids, seeds, initial_lr,
         fc.bs, fc.C, ex.server_arena.data, ex.arena.data, ex.arena.grad,
         round_accum, fc.work_f, fc.work_i, fc.work_b, fc.work_d,
         fc.lr_t, fc.max_norm, fc.p1, fc.p2,
-        ex._round_stats, ex._round_loss, fc.use_bf16)
+        ex._round_stats, ex._round_loss, fc.use_bf16, mu=mu)
     ex.perf_acc["clients"] = ex.perf_acc.get("clients", 0) + K
     return round_outputs(client_ids, counts, fc.bs, ex._round_loss,
                          ex._round_stats, ex.arena.total)

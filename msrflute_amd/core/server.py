@@ -26,7 +26,7 @@ import torch
 from ..comm.runtime import FedRuntime
 from ..strategies import select_strategy
 from ..utils import log_metric, print_rank, update_json_log
-from .client import Client, ClientExecutor
+from .client import Client, ClientExecutor, fused_round_mu
 from .evaluation import Evaluation
 from .trainer import (ModelUpdater, Trainer, flush_saves, get_lr,
                       set_component_wise_lr)
@@ -315,14 +315,15 @@ class OptimizationServer:
         # trains every local client (copy-in, epoch, pseudo-grad,
         # accumulate all inside the extension)
         fused_outputs = None
-        # The fused driver trains plain SGD with no proximal term, so it
-        # is only equivalent to the eager path under FedAvg (FedProx adds
-        # (mu/2)||w-w_g||^2 every local step — reference trainer.py:463).
+        # The fused drivers train plain SGD (FedAvg) or SGD with the exact
+        # per-batch proximal term (FedProx); fused_round_mu is the gate.
         if (hasattr(self.executor, "run_fused_round_batch")
-                and self.config["strategy"] == "FedAvg"
+                and fused_round_mu(
+                    self.config["strategy"], self.config["client_config"],
+                    self.config.get("model_config"),
+                    apply_privacy_metrics) is not None
                 and self.config["client_config"].get("use_fused_round",
-                                                     True)
-                and not apply_privacy_metrics):
+                                                     True)):
             seeds = [rt.round_rng(i, salt=100 + c).getrandbits(62)
                      for c in my_clients]
             fused_outputs = self.executor.run_fused_round_batch(

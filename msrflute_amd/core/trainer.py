@@ -294,7 +294,9 @@ class Trainer(TrainerBase):
         """Reference: trainer.py:341-414 (and 416-501 when ``prox`` is set:
         prox = (mu, w_global_flat))."""
         fast_ok = prox is None and not apply_privacy_metrics
-        if fast_ok and self.fused_cnn is not None:
+        # the fused CNN epoch forms the proximal term in its clip/SGD
+        # kernels; the hipGraph epochs below stay FedAvg-only
+        if not apply_privacy_metrics and self.fused_cnn is not None:
             ds = getattr(self.train_dataloader, "dataset", None)
             if (ds is not None and torch.is_tensor(getattr(ds, "x", None))
                     and ds.x.is_cuda and torch.is_tensor(getattr(ds, "y", None))
@@ -302,7 +304,7 @@ class Trainer(TrainerBase):
                     and getattr(self.train_dataloader, "shuffle", False)
                     and (desired_max_samples is None
                          or desired_max_samples >= len(ds.x))):
-                return self._run_epoch_fused_cnn(ds)
+                return self._run_epoch_fused_cnn(ds, prox)
         if (self.graph_cache is not None and fast_ok
                 and self.graph_cache.supports()):
             return self._run_train_epoch_graphed(desired_max_samples)
@@ -465,15 +467,17 @@ class Trainer(TrainerBase):
         self._finalize_sufficient_stats()
         return num_samples, loss_total
 
-    def _run_epoch_fused_cnn(self, ds):
+    def _run_epoch_fused_cnn(self, ds, prox=None):
         """One local epoch via the hand-written fused CNN kernels
-        (ops/fused_cnn.py) — no autograd, no graphs."""
+        (ops/fused_cnn.py) — no autograd, no graphs.  ``prox`` as in
+        ``run_train_epoch``."""
         self.reset_gradient_power()
         fc = self.fused_cnn
         fc.lr_t  # noqa: B018 — touch to assert constructed
         lr = get_lr(self.optimizer) if self.optimizer is not None else 0.0
         order = torch.randperm(len(ds.x))
-        n, n_batches = fc.run_epoch(ds.x, ds.y, order, lr, self.round_seed)
+        n, n_batches = fc.run_epoch(ds.x, ds.y, order, lr, self.round_seed,
+                                    prox=prox)
         self.step += n_batches
         if self.lr_scheduler is not None:
             self.lr_scheduler.step()

@@ -211,6 +211,18 @@ static CnnWorkspace slice_ws(torch::Tensor& work_f, torch::Tensor& work_i,
   return ws;
 }
 
+// FedProx arguments shared by the CNN / clip entries: mu == 0 is plain
+// SGD and needs no server vector; mu > 0 needs the [P] server weights
+static const float* prox_server(const c10::optional<torch::Tensor>& server,
+                                double mu, long long P) {
+  TORCH_CHECK(mu >= 0.0, "mu must be >= 0");
+  if (mu == 0.0) return nullptr;
+  TORCH_CHECK(server.has_value(), "mu > 0 needs the server weights");
+  check_flat(*server, "server");
+  TORCH_CHECK(server->numel() == P, "server must hold P floats");
+  return server->data_ptr<float>();
+}
+
 // fully-fused CNN-FEMNIST client epoch (fused_cnn.hip): one host call
 // trains a whole local epoch — fwd, bwd, clip+stats, SGD per batch —
 // bypassing autograd and hip graphs entirely.
@@ -221,8 +233,10 @@ void cnn_epoch(torch::Tensor shard_x, torch::Tensor shard_y,
                torch::Tensor work_b, torch::Tensor work_d,
                torch::Tensor lr_t, double max_norm, double p1, double p2,
                torch::Tensor stats_acc, torch::Tensor loss_acc,
-               int64_t seed, bool use_bf16) {
+               int64_t seed, bool use_bf16,
+               c10::optional<torch::Tensor> server, double mu) {
   check_flat(params, "params"); check_flat(grads, "grads");
+  const float* server_p = prox_server(server, mu, params.numel());
   check_flat(lr_t, "lr_t"); check_flat(stats_acc, "stats_acc");
   check_flat(loss_acc, "loss_acc"); check_flat(work_f, "work_f");
   TORCH_CHECK(shard_x.is_cuda() && shard_x.is_contiguous() &&
@@ -246,7 +260,7 @@ void cnn_epoch(torch::Tensor shard_x, torch::Tensor shard_y,
                    lr_t.data_ptr<float>(), (float)max_norm, (float)p1,
                    (float)p2, stats_acc.data_ptr<float>(),
                    loss_acc.data_ptr<float>(), (unsigned long long)seed,
-                   cur_stream(), 0, use_bf16 ? 1 : 0);
+                   cur_stream(), 0, use_bf16 ? 1 : 0, server_p, (float)mu);
 }
 
 // whole-round driver: K clients in ONE host call (copy-in, fused epoch,
@@ -261,7 +275,8 @@ void cnn_round(torch::Tensor shard_x, torch::Tensor shard_y,
                torch::Tensor work_b, torch::Tensor work_d,
                torch::Tensor lr_t, double max_norm, double p1, double p2,
                torch::Tensor stats_out, torch::Tensor loss_out,
-               bool use_bf16) {
+               bool use_bf16, double mu) {
+  TORCH_CHECK(mu >= 0.0, "mu must be >= 0");
   check_flat(server_params, "server_params"); check_flat(params, "params");
   check_flat(grads, "grads"); check_flat(round_accum, "round_accum");
   TORCH_CHECK(orders_dev.is_cuda() && orders_dev.scalar_type() == torch::kInt64);
@@ -319,7 +334,8 @@ void cnn_round(torch::Tensor shard_x, torch::Tensor shard_y,
       params.data_ptr<float>(), grads.data_ptr<float>(),
       round_accum.data_ptr<float>(), ws, lr_t.data_ptr<float>(),
       (float)max_norm, (float)p1, (float)p2, stats_out.data_ptr<float>(),
-      loss_out.data_ptr<float>(), cur_stream(), use_bf16 ? 1 : 0);
+      loss_out.data_ptr<float>(), cur_stream(), use_bf16 ? 1 : 0,
+      (float)mu);
 }
 
 // fused LSTM sequence recurrence (lstm_seq.hip): all T steps in one
@@ -732,7 +748,8 @@ void cnn_round_mega(torch::Tensor shard_x, torch::Tensor shard_y,
                     torch::Tensor work_b, torch::Tensor work_d,
                     torch::Tensor lr_t, double max_norm, double p1,
                     double p2, torch::Tensor stats_out,
-                    torch::Tensor loss_out, bool use_bf16) {
+                    torch::Tensor loss_out, bool use_bf16, double mu) {
+  TORCH_CHECK(mu >= 0.0, "mu must be >= 0");
   check_flat(server_params, "server_params");
   check_flat(params_stack, "params_stack");
   check_flat(grads_stack, "grads_stack");
@@ -795,7 +812,8 @@ void cnn_round_mega(torch::Tensor shard_x, torch::Tensor shard_y,
   unsigned char* m3 = u + (long long)G * 9216 * 2;
   TORCH_CHECK(work_b.numel() >= (long long)G * (9216 * 2 + 128),
               "mega byte workspace too small");
-  TORCH_CHECK(work_d.numel() >= 2 * K, "mega double workspace too small");
+  TORCH_CHECK(work_d.numel() >= (mu > 0.0 ? 3 : 2) * K,
+              "mega double workspace too small");
   launch_cnn_round_mega(
       shard_x.data_ptr<float>(),
       reinterpret_cast<const long long*>(shard_y.data_ptr<int64_t>()),
@@ -813,28 +831,48 @@ void cnn_round_mega(torch::Tensor shard_x, torch::Tensor shard_y,
       work_i.data_ptr<int>(), pidx, m2, m3, work_d.data_ptr<double>(),
       lr_t.data_ptr<float>(), (float)max_norm, (float)p1, (float)p2,
       stats_out.data_ptr<float>(), loss_out.data_ptr<float>(),
-      cur_stream(), use_bf16 ? 1 : 0);
+      cur_stream(), use_bf16 ? 1 : 0, (float)mu);
 }
 
 // per-client clip + sufficient stats + SGD over a K-stacked flat arena
 // (graph-capture safe; stats_out[2k] accumulates clipped Σg / Σg²)
 void mega_clip_sgd(torch::Tensor params_stack, torch::Tensor grads_stack,
                    int64_t K, torch::Tensor acc2k, double max_norm,
-                   torch::Tensor lr_t, torch::Tensor stats_out) {
+                   torch::Tensor lr_t, torch::Tensor stats_out,
+                   c10::optional<torch::Tensor> server, double mu,
+                   c10::optional<torch::Tensor> active,
+                   c10::optional<torch::Tensor> loss_out) {
   check_flat(params_stack, "params_stack");
   check_flat(grads_stack, "grads_stack");
   check_flat(lr_t, "lr_t"); check_flat(stats_out, "stats_out");
   TORCH_CHECK(K > 0 && params_stack.numel() % K == 0 &&
               params_stack.numel() == grads_stack.numel());
   TORCH_CHECK(acc2k.is_cuda() && acc2k.scalar_type() == torch::kFloat64 &&
-              acc2k.numel() >= 2 * K);
+              acc2k.numel() >= (mu > 0.0 ? 3 : 2) * K);
   TORCH_CHECK(stats_out.numel() >= 2 * K);
   long long P = params_stack.numel() / K;
+  // FedProx (mu > 0): gp = g + mu (w - server) for the clients whose
+  // `active` byte is set (absent = all); loss_out[k] += 0.5 mu ||w - server||^2
+  const float* server_p = prox_server(server, mu, P);
+  const unsigned char* active_p = nullptr;
+  float* loss_p = nullptr;
+  if (mu > 0.0 && active.has_value()) {
+    TORCH_CHECK(active->is_cuda() && active->is_contiguous() &&
+                (active->scalar_type() == torch::kBool ||
+                 active->scalar_type() == torch::kUInt8) &&
+                active->numel() == K, "active must be K bool/uint8 on device");
+    active_p = static_cast<const unsigned char*>(active->data_ptr());
+  }
+  if (mu > 0.0 && loss_out.has_value()) {
+    check_flat(*loss_out, "loss_out");
+    TORCH_CHECK(loss_out->numel() >= K);
+    loss_p = loss_out->data_ptr<float>();
+  }
   launch_mega_clip_sgd(params_stack.data_ptr<float>(),
                        grads_stack.data_ptr<float>(), P, (int)K,
                        acc2k.data_ptr<double>(), (float)max_norm,
                        lr_t.data_ptr<float>(), stats_out.data_ptr<float>(),
-                       cur_stream());
+                       cur_stream(), server_p, (float)mu, active_p, loss_p);
 }
 
 void mega_pseudo_accum(torch::Tensor grads_stack, torch::Tensor server,
@@ -860,8 +898,16 @@ void mega_pseudo_accum(torch::Tensor grads_stack, torch::Tensor server,
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   // output rows per block of the f32 conv2 forward (its slab seams)
   m.attr("CONV2_FWD_SLAB_ROWS") = CONV2_FWD_SLAB_ROWS;
-  m.def("cnn_round_mega", &cnn_round_mega);
-  m.def("mega_clip_sgd", &mega_clip_sgd);
+  // FedProx arguments trail with defaults: the FedAvg positional calls
+  // stay as they were
+  m.def("cnn_round_mega", &cnn_round_mega,
+        py::arg("shard_x"), py::arg("shard_y"), py::arg("orders_dev"),
+        py::arg("row_bases_dev"), py::arg("order_offs_dev"), py::arg("counts_dev"), py::arg("counts_host"), py::arg("weights_dev"), py::arg("seeds_dev"), py::arg("bs"), py::arg("C"), py::arg("server_params"), py::arg("params_stack"), py::arg("grads_stack"), py::arg("round_accum"), py::arg("work_f"), py::arg("work_i"), py::arg("work_b"), py::arg("work_d"), py::arg("lr_t"), py::arg("max_norm"), py::arg("p1"), py::arg("p2"), py::arg("stats_out"), py::arg("loss_out"), py::arg("use_bf16"),
+        py::arg("mu") = 0.0);
+  m.def("mega_clip_sgd", &mega_clip_sgd,
+        py::arg("params_stack"), py::arg("grads_stack"), py::arg("K"), py::arg("acc2k"), py::arg("max_norm"), py::arg("lr_t"), py::arg("stats_out"),
+        py::arg("server") = py::none(), py::arg("mu") = 0.0,
+        py::arg("active") = py::none(), py::arg("loss_out") = py::none());
   m.def("mega_pseudo_accum", &mega_pseudo_accum);
   m.def("dbg_mfma_bf16_probe", &dbg_mfma_bf16_probe);
   m.def("dbg_conv2_fwd_mfma_bf16", &dbg_conv2_fwd_mfma_bf16);
@@ -894,8 +940,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("segmented_sqnorm", &segmented_sqnorm);
   m.def("quant_bin_mask", &quant_bin_mask);
   m.def("gru_gates", &gru_gates);
-  m.def("cnn_epoch", &cnn_epoch);
-  m.def("cnn_round", &cnn_round);
+  m.def("cnn_epoch", &cnn_epoch,
+        py::arg("shard_x"), py::arg("shard_y"), py::arg("order"), py::arg("bs"), py::arg("C"), py::arg("params"), py::arg("grads"), py::arg("work_f"), py::arg("work_i"), py::arg("work_b"), py::arg("work_d"), py::arg("lr_t"), py::arg("max_norm"), py::arg("p1"), py::arg("p2"), py::arg("stats_acc"), py::arg("loss_acc"), py::arg("seed"), py::arg("use_bf16"),
+        py::arg("server") = py::none(), py::arg("mu") = 0.0);
+  m.def("cnn_round", &cnn_round,
+        py::arg("shard_x"), py::arg("shard_y"), py::arg("orders_dev"), py::arg("row_bases"), py::arg("order_offs"), py::arg("counts"), py::arg("weights"), py::arg("seeds"), py::arg("bs"), py::arg("C"), py::arg("server_params"), py::arg("params"), py::arg("grads"), py::arg("round_accum"), py::arg("work_f"), py::arg("work_i"), py::arg("work_b"), py::arg("work_d"), py::arg("lr_t"), py::arg("max_norm"), py::arg("p1"), py::arg("p2"), py::arg("stats_out"), py::arg("loss_out"), py::arg("use_bf16"),
+        py::arg("mu") = 0.0);
   m.def("lstm_seq_fwd", &lstm_seq_fwd);
   m.def("gru_seq_fwd", &gru_seq_fwd);
   m.def("gru_seq_bwd", &gru_seq_bwd);

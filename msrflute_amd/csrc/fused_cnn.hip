@@ -127,13 +127,13 @@ __global__ void k_gather_mb(const float* __restrict__ shard_x,
                             const long long* __restrict__ counts,
                             int t, int bs, int K,
                             float* __restrict__ xb, int* __restrict__ yb,
-                            double* __restrict__ acc2k) {
+                            double* __restrict__ acc2k, int n_acc) {
   int G = K * bs;
   // first kernel of a batch-step: zero the clip's per-client sum / sumsq
-  // slots (their last reader, the previous step's k_clip_sgd_mb, precedes
-  // this kernel in stream order)
+  // slots (2K; 3K under FedProx) — their last reader, the previous step's
+  // k_clip_sgd_mb, precedes this kernel in stream order
   if (blockIdx.x == 0)
-    for (int q = threadIdx.x; q < 2 * K; q += blockDim.x) acc2k[q] = 0.0;
+    for (int q = threadIdx.x; q < n_acc; q += blockDim.x) acc2k[q] = 0.0;
   for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
        i < (long long)G * 784; i += (long long)gridDim.x * blockDim.x) {
     int g = (int)(i / 784), j = (int)(i % 784);
@@ -1392,54 +1392,132 @@ __global__ void k_conv1_bwd_w_mb(const float* __restrict__ x,
 // (few hundred atomics per client per step).  Stage 2 (k_clip_sgd_mb):
 // per-client scale + SGD in one elementwise pass, whose block 0 also
 // accumulates the K clients' clipped stats.
+//
+// FedProx (the ProxArgs instantiations of both kernels; NoProx, an empty
+// argument, instantiates the FedAvg code unchanged): the
+// gradient both passes see is gp = g + mu * (w - w_g), formed in registers
+// by prox_grad() and never stored unless STORE_G; a third f64 slot per
+// client, acc[2K + k], collects sum (w - w_g)^2 for the reported loss.
+// The term exists only for a client that is ACTIVE at this step: an idle
+// client (epoch finished / masked) has g == 0 exactly and must not move,
+// although its w != w_g.  Idleness is a select on mu, not a branch around
+// the loads: mu_eff = 0 makes gp = fma(0, w - w_g, g) = g bit for bit.
+struct NoProx { static constexpr bool PROX = false; };
+struct ProxArgs {
+  static constexpr bool PROX = true;
+  const float* params;       // [K * P] weights before the step (sumsq pass)
+  int K;
+  const float* server;       // [P] server weights w_g, shared by all K
+  float mu;
+  // active predicate, first non-null wins; neither = every client active
+  const long long* counts;   // mega driver: active iff t * bs < counts[k]
+  int t, bs;
+  const unsigned char* active;  // stand-alone entry: per-client mask [K]
+  float* loss_out;           // [K] += 0.5 * mu * sum (w - w_g)^2, or null
+};
+
+__device__ __forceinline__ bool prox_active(const NoProx&, int) {
+  return true;
+}
+__device__ __forceinline__ bool prox_active(const ProxArgs& a, int k) {
+  if (a.counts) return mega_Bk(a.counts, k, a.t, a.bs) > 0;
+  if (a.active) return a.active[k] != 0;
+  return true;
+}
+
+// the ONE place gp is formed: explicit single roundings, so the value
+// whose square k_sumsq sums is bit for bit the value k_clip_sgd applies
+__device__ __forceinline__ float prox_grad(float g, float w, float wg,
+                                           float mu_eff) {
+  return fmaf(mu_eff, __fsub_rn(w, wg), g);
+}
+
 // one block per (client, contiguous chunk): block-local tree reduce,
-// ONE f64 atomicAdd pair per block (~K * ceil(P/65536) atomics per step)
+// ONE f64 atomicAdd pair (PROX: triple) per block
+// (~K * ceil(P/32768) atomics per step)
 #define SUMSQ_CHUNK 32768
+template <typename PX>
 __global__ void k_sumsq_mb(const float* __restrict__ grads, long long P,
-                           int blocks_per_k, double* __restrict__ acc) {
+                           int blocks_per_k, double* __restrict__ acc,
+                           PX px) {
+  constexpr bool PROX = PX::PROX;
   int k = blockIdx.x / blocks_per_k;
   int c = blockIdx.x % blocks_per_k;
   long long lo = (long long)c * SUMSQ_CHUNK;
   long long hi = lo + SUMSQ_CHUNK;
   if (hi > P) hi = P;
   const float* g = grads + (long long)k * P;
+  const float* w = nullptr;
+  float mu_eff = 0.f;
+  if constexpr (PROX) {
+    w = px.params + (long long)k * P;
+    mu_eff = prox_active(px, k) ? px.mu : 0.f;
+  }
   // float4 loads + independent accumulator pairs break the dependent
   // f64-add chain (was ~74 us per step at 190 underfilled blocks)
   double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
   double q0 = 0.0, q1 = 0.0, q2 = 0.0, q3 = 0.0;
+  double r0 = 0.0, r1 = 0.0, r2 = 0.0, r3 = 0.0;  // PROX: (w - w_g)^2
   // scalar loads (the k*P segment bases are not 16 B aligned); the win
   // is the 4 independent f64 accumulator chains
   long long i = lo + (long long)threadIdx.x * 4;
   for (; i + 3 < hi; i += (long long)blockDim.x * 4) {
-    double a = g[i], b = g[i + 1], cc = g[i + 2], d = g[i + 3];
+    double a, b, cc, d;
+    if constexpr (PROX) {
+      float d0 = __fsub_rn(w[i], px.server[i]);
+      float d1 = __fsub_rn(w[i + 1], px.server[i + 1]);
+      float d2 = __fsub_rn(w[i + 2], px.server[i + 2]);
+      float d3 = __fsub_rn(w[i + 3], px.server[i + 3]);
+      a = prox_grad(g[i], w[i], px.server[i], mu_eff);
+      b = prox_grad(g[i + 1], w[i + 1], px.server[i + 1], mu_eff);
+      cc = prox_grad(g[i + 2], w[i + 2], px.server[i + 2], mu_eff);
+      d = prox_grad(g[i + 3], w[i + 3], px.server[i + 3], mu_eff);
+      r0 += (double)d0 * d0; r1 += (double)d1 * d1;
+      r2 += (double)d2 * d2; r3 += (double)d3 * d3;
+    } else {
+      a = g[i]; b = g[i + 1]; cc = g[i + 2]; d = g[i + 3];
+    }
     s0 += a; q0 += a * a;
     s1 += b; q1 += b * b;
     s2 += cc; q2 += cc * cc;
     s3 += d; q3 += d * d;
   }
   for (long long j = i; j < hi; ++j) {  // ragged tail (P % 4)
-    double v = (double)g[j];
+    double v;
+    if constexpr (PROX) {
+      float dj = __fsub_rn(w[j], px.server[j]);
+      v = (double)prox_grad(g[j], w[j], px.server[j], mu_eff);
+      r0 += (double)dj * dj;
+    } else {
+      v = (double)g[j];
+    }
     s0 += v; q0 += v * v;
   }
   double fs = (s0 + s1) + (s2 + s3);
   double fq = (q0 + q1) + (q2 + q3);
-  {
-  }
+  double fr = (r0 + r1) + (r2 + r3);
   for (int d = 32; d > 0; d >>= 1) {
     fs += __shfl_down(fs, d, 64);
     fq += __shfl_down(fq, d, 64);
+    if constexpr (PROX) fr += __shfl_down(fr, d, 64);
   }
-  __shared__ double lds[2 * 4];
+  __shared__ double lds[(PROX ? 3 : 2) * 4];
+  constexpr int NS = PROX ? 3 : 2;
   int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  if (lane == 0) { lds[2 * wave] = fs; lds[2 * wave + 1] = fq; }
+  if (lane == 0) {
+    lds[NS * wave] = fs; lds[NS * wave + 1] = fq;
+    if constexpr (PROX) lds[NS * wave + 2] = fr;
+  }
   __syncthreads();
   if (threadIdx.x == 0) {
-    double ts = 0.0, tq = 0.0;
-    for (int w = 0; w < (int)blockDim.x / 64; ++w) {
-      ts += lds[2 * w]; tq += lds[2 * w + 1];
+    double ts = 0.0, tq = 0.0, tr = 0.0;
+    for (int wv = 0; wv < (int)blockDim.x / 64; ++wv) {
+      ts += lds[NS * wv]; tq += lds[NS * wv + 1];
+      if constexpr (PROX) tr += lds[NS * wv + 2];
     }
     atomicAdd(acc + 2 * k, ts);
     atomicAdd(acc + 2 * k + 1, tq);
+    if constexpr (PROX) atomicAdd(acc + 2 * px.K + k, tr);
   }
 }
 
@@ -1456,12 +1534,13 @@ __device__ __forceinline__ float clip_scale(const double* __restrict__ acc,
 // without that store; the stand-alone entry keeps it.  i only grows, so
 // a thread re-derives its client and the scale when it crosses a segment
 // end, not per element.
-template <bool STORE_G>
+template <bool STORE_G, typename PX>
 __global__ void k_clip_sgd_mb(float* __restrict__ params,
                               float* __restrict__ grads, long long P, int K,
                               const double* __restrict__ acc, float max_norm,
                               float eps, const float* __restrict__ lr_t,
-                              float* __restrict__ stats_out) {
+                              float* __restrict__ stats_out, PX px) {
+  constexpr bool PROX = PX::PROX;
   long long total = (long long)K * P;
   float lr = lr_t[0];
   // block 0 also accumulates the per-client clipped stats:
@@ -1471,21 +1550,36 @@ __global__ void k_clip_sgd_mb(float* __restrict__ params,
       float scale = clip_scale(acc, k, max_norm, eps);
       stats_out[2 * k] += scale * (float)acc[2 * k];
       stats_out[2 * k + 1] += scale * scale * (float)acc[2 * k + 1];
+      if constexpr (PROX)
+        // the regulariser of an ACTIVE client's step, next to its CE
+        if (px.loss_out && prox_active(px, k))
+          px.loss_out[k] += (float)(0.5 * (double)px.mu * acc[2 * K + k]);
     }
   long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
   if (i >= total) return;
   int k = (int)(i / P);
   long long seg_end = (long long)(k + 1) * P;
   float scale = clip_scale(acc, k, max_norm, eps);
+  float mu_eff = 0.f;
+  if constexpr (PROX) mu_eff = prox_active(px, k) ? px.mu : 0.f;
   for (; i < total; i += (long long)gridDim.x * blockDim.x) {
     if (i >= seg_end) {
       k = (int)(i / P);
       seg_end = (long long)(k + 1) * P;
       scale = clip_scale(acc, k, max_norm, eps);
+      if constexpr (PROX) mu_eff = prox_active(px, k) ? px.mu : 0.f;
     }
-    float gv = grads[i] * scale;
-    if constexpr (STORE_G) grads[i] = gv;
-    params[i] -= lr * gv;
+    if constexpr (PROX) {
+      float w = params[i];
+      float gv = prox_grad(grads[i], w, px.server[i - (long long)k * P],
+                           mu_eff) * scale;
+      if constexpr (STORE_G) grads[i] = gv;
+      params[i] = w - lr * gv;
+    } else {
+      float gv = grads[i] * scale;
+      if constexpr (STORE_G) grads[i] = gv;
+      params[i] -= lr * gv;
+    }
   }
 }
 
@@ -1811,7 +1905,8 @@ extern "C" void launch_cnn_epoch(
     long long n, int bs, int C, float* params, float* grads,
     CnnWorkspace ws, const float* lr_t, float max_norm, float p1, float p2,
     float* stats_acc, float* loss_acc, unsigned long long seed,
-    hipStream_t s, long long row_base, int use_bf16) {
+    hipStream_t s, long long row_base, int use_bf16,
+    const float* server_params, float mu) {
   static const bool epoch_dbg = getenv("CNN_EPOCH_DEBUG") != nullptr;
   CnnOffsets o = cnn_offsets(C);
   long long P = o.total;
@@ -1916,6 +2011,25 @@ extern "C" void launch_cnn_epoch(
     hipLaunchKernelGGL(k_conv1_bwd_w_mb, dim3(32), dim3(1024), 0, s,
                        ws.xb, ws.dz1, grads, P, o.w1, o.b1, B, K);
     EPOCH_CHK("k_conv1_bwd_w_mb");
+    if (mu > 0.f) {
+      // FedProx: the PROX pair at K = 1, every step active; forms
+      // g + mu (w - w_g) in registers and adds the regulariser to loss_acc
+      ProxArgs px{params, K, server_params, mu, nullptr, 0, 0, nullptr,
+                  loss_acc};
+      hipMemsetAsync(ws.red_partials, 0, 3 * sizeof(double), s);
+      int blocks_per_k = (int)((P + SUMSQ_CHUNK - 1) / SUMSQ_CHUNK);
+      hipLaunchKernelGGL(k_sumsq_mb<ProxArgs>, dim3(blocks_per_k),
+                         dim3(FBLK), 0, s, grads, P, blocks_per_k,
+                         ws.red_partials, px);
+      EPOCH_CHK("k_sumsq_mb<ProxArgs>");
+      int gkp = (int)((P + FBLK - 1) / FBLK); if (gkp > 4096) gkp = 4096;
+      hipLaunchKernelGGL((k_clip_sgd_mb<false, ProxArgs>), dim3(gkp),
+                         dim3(FBLK), 0, s, params, grads, P, K,
+                         ws.red_partials, max_norm, 1e-6f, lr_t, stats_acc,
+                         px);
+      EPOCH_CHK("k_clip_sgd_mb<ProxArgs>");
+      continue;
+    }
     // fused clip + sufficient stats + SGD on the whole arena
     hipMemsetAsync(ws.red_acc, 0, 2 * sizeof(double), s);
     launch_sum_sumsq2(grads, o.total, ws.red_partials, ws.red_acc, s);
@@ -1943,7 +2057,7 @@ extern "C" void launch_cnn_round(
     const float* server_params, float* params, float* grads,
     float* round_accum, CnnWorkspace ws, const float* lr_t, float max_norm,
     float p1, float p2, float* stats_out, float* loss_out,
-    hipStream_t s, int use_bf16) {
+    hipStream_t s, int use_bf16, float mu) {
   CnnOffsets o = cnn_offsets(C);
   int gp = (int)((o.total + FBLK - 1) / FBLK);
   if (gp > 2048) gp = 2048;
@@ -1953,7 +2067,7 @@ extern "C" void launch_cnn_round(
     launch_cnn_epoch(shard_x, shard_y, orders + order_offs[k], counts[k],
                      bs, C, params, grads, ws, lr_t, max_norm, p1, p2,
                      stats_out + 2 * k, loss_out + k, seeds[k], s,
-                     row_bases[k], use_bf16);
+                     row_bases[k], use_bf16, server_params, mu);
     hipLaunchKernelGGL(k_cnn_pseudo_grad, dim3(gp), dim3(FBLK), 0, s,
                        grads, server_params, params, weights[k], o.total);
     hipLaunchKernelGGL(k_cnn_axpy, dim3(gp), dim3(FBLK), 0, s,
@@ -1979,10 +2093,12 @@ extern "C" void launch_cnn_round_mega(
     int* yb, unsigned char* pidx, unsigned char* m2, unsigned char* m3,
     double* acc2k,
     const float* lr_t, float max_norm, float p1, float p2,
-    float* stats_out, float* loss_out, hipStream_t s, int use_bf16) {
+    float* stats_out, float* loss_out, hipStream_t s, int use_bf16,
+    float mu) {
   CnnOffsets o = cnn_offsets(C);
   long long P = o.total;
   int G = K * bs;
+  const bool prox = mu > 0.f;  // FedProx: acc2k holds 3K doubles
   int max_batches = 0;
   for (int k = 0; k < K; ++k) {
     int nb = (int)((counts_host[k] + bs - 1) / bs);
@@ -1998,7 +2114,7 @@ extern "C" void launch_cnn_round_mega(
     hipLaunchKernelGGL(k_gather_mb, dim3((G * 784 + FBLK - 1) / FBLK),
                        dim3(FBLK), 0, s, shard_x, shard_y, orders_dev,
                        row_bases_dev, order_offs_dev, counts_dev, t, bs, K,
-                       xb, yb, acc2k);
+                       xb, yb, acc2k, prox ? 3 * K : 2 * K);
     hipLaunchKernelGGL(k_conv1_fwd_mb,
                        dim3((int)(((long long)G * 21632 + FBLK - 1) / FBLK)),
                        dim3(FBLK), 0, s, xb, params_stack, P, o.w1, o.b1,
@@ -2079,11 +2195,25 @@ extern "C" void launch_cnn_round_mega(
                        xb, dz1, grads_stack, P, o.w1, o.b1, bs, K);
     // acc2k was zeroed by this step's k_gather_mb
     int blocks_per_k = (int)((P + SUMSQ_CHUNK - 1) / SUMSQ_CHUNK);
-    hipLaunchKernelGGL(k_sumsq_mb, dim3(K * blocks_per_k), dim3(FBLK), 0, s,
-                       grads_stack, P, blocks_per_k, acc2k);
-    hipLaunchKernelGGL(k_clip_sgd_mb<false>, dim3(gkp), dim3(FBLK), 0, s,
-                       params_stack, grads_stack, P, K, acc2k, max_norm,
-                       1e-6f, lr_t, stats_out);
+    if (prox) {
+      // same two dispatches; idle clients (t * bs >= counts[k]) get no
+      // proximal term and no regulariser
+      ProxArgs px{params_stack, K, server_params, mu, counts_dev, t, bs,
+                  nullptr, loss_out};
+      hipLaunchKernelGGL(k_sumsq_mb<ProxArgs>, dim3(K * blocks_per_k),
+                         dim3(FBLK), 0, s, grads_stack, P, blocks_per_k,
+                         acc2k, px);
+      hipLaunchKernelGGL((k_clip_sgd_mb<false, ProxArgs>), dim3(gkp),
+                         dim3(FBLK), 0, s, params_stack, grads_stack, P, K,
+                         acc2k, max_norm, 1e-6f, lr_t, stats_out, px);
+      continue;
+    }
+    hipLaunchKernelGGL(k_sumsq_mb<NoProx>, dim3(K * blocks_per_k),
+                       dim3(FBLK), 0, s, grads_stack, P, blocks_per_k, acc2k,
+                       NoProx{});
+    hipLaunchKernelGGL((k_clip_sgd_mb<false, NoProx>), dim3(gkp), dim3(FBLK),
+                       0, s, params_stack, grads_stack, P, K, acc2k, max_norm,
+                       1e-6f, lr_t, stats_out, NoProx{});
   }
   hipLaunchKernelGGL(k_pseudo_grad_mb, dim3(gkp), dim3(FBLK), 0, s,
                      grads_stack, server_params, params_stack, weights_dev,
@@ -2101,16 +2231,32 @@ extern "C" void launch_cnn_round_mega(
 extern "C" void launch_mega_clip_sgd(float* params_stack, float* grads_stack,
                                      long long P, int K, double* acc2k,
                                      float max_norm, const float* lr_t,
-                                     float* stats_out, hipStream_t s) {
-  hipMemsetAsync(acc2k, 0, 2 * K * sizeof(double), s);
+                                     float* stats_out, hipStream_t s,
+                                     const float* server, float mu,
+                                     const unsigned char* active,
+                                     float* loss_out) {
   int blocks_per_k = (int)((P + SUMSQ_CHUNK - 1) / SUMSQ_CHUNK);
-  hipLaunchKernelGGL(k_sumsq_mb, dim3(K * blocks_per_k), dim3(FBLK), 0, s,
-                     grads_stack, P, blocks_per_k, acc2k);
   long long kp = (long long)K * P;
   int gkp = (int)((kp + FBLK - 1) / FBLK); if (gkp > 4096) gkp = 4096;
-  hipLaunchKernelGGL(k_clip_sgd_mb<true>, dim3(gkp), dim3(FBLK), 0, s,
-                     params_stack, grads_stack, P, K, acc2k, max_norm,
-                     1e-6f, lr_t, stats_out);
+  if (mu > 0.f) {
+    // FedProx: acc2k holds 3K doubles; the stored gradient is scale * gp
+    ProxArgs px{params_stack, K, server, mu, nullptr, 0, 0, active,
+                loss_out};
+    hipMemsetAsync(acc2k, 0, 3 * K * sizeof(double), s);
+    hipLaunchKernelGGL(k_sumsq_mb<ProxArgs>, dim3(K * blocks_per_k),
+                       dim3(FBLK), 0, s, grads_stack, P, blocks_per_k, acc2k,
+                       px);
+    hipLaunchKernelGGL((k_clip_sgd_mb<true, ProxArgs>), dim3(gkp),
+                       dim3(FBLK), 0, s, params_stack, grads_stack, P, K,
+                       acc2k, max_norm, 1e-6f, lr_t, stats_out, px);
+    return;
+  }
+  hipMemsetAsync(acc2k, 0, 2 * K * sizeof(double), s);
+  hipLaunchKernelGGL(k_sumsq_mb<NoProx>, dim3(K * blocks_per_k), dim3(FBLK),
+                     0, s, grads_stack, P, blocks_per_k, acc2k, NoProx{});
+  hipLaunchKernelGGL((k_clip_sgd_mb<true, NoProx>), dim3(gkp), dim3(FBLK), 0,
+                     s, params_stack, grads_stack, P, K, acc2k, max_norm,
+                     1e-6f, lr_t, stats_out, NoProx{});
 }
 
 extern "C" void launch_mega_pseudo_accum(float* grads_stack,

@@ -114,13 +114,17 @@ void launch_gru_seq_bwd(const float* gates, const float* ghn,
                         const float* dh_out, float* dgi, float* dgh,
                         int B, int T, hipStream_t s);
 
-// fused_cnn.hip — drivers
+// fused_cnn.hip — drivers.  mu > 0 (FedProx) makes the clip/SGD tail of
+// every step use g + mu (w - server) and adds 0.5 mu ||w - server||^2 to
+// the step's loss, for the clients active at that step; mu == 0 launches
+// exactly the FedAvg kernels.
 void launch_cnn_epoch(
     const float* shard_x, const long long* shard_y, const long long* order,
     long long n, int bs, int C, float* params, float* grads,
     CnnWorkspace ws, const float* lr_t, float max_norm, float p1, float p2,
     float* stats_acc, float* loss_acc, unsigned long long seed,
-    hipStream_t s, long long row_base, int use_bf16);
+    hipStream_t s, long long row_base, int use_bf16,
+    const float* server_params, float mu);
 void launch_cnn_round(
     const float* shard_x, const long long* shard_y,
     const long long* orders,            // concatenated per-client shuffles
@@ -133,7 +137,7 @@ void launch_cnn_round(
     const float* server_params, float* params, float* grads,
     float* round_accum, CnnWorkspace ws, const float* lr_t, float max_norm,
     float p1, float p2, float* stats_out, float* loss_out,
-    hipStream_t s, int use_bf16);
+    hipStream_t s, int use_bf16, float mu);
 void launch_cnn_round_mega(
     const float* shard_x, const long long* shard_y,
     const long long* orders_dev,
@@ -147,12 +151,16 @@ void launch_cnn_round_mega(
     float* dlogits, float* dz3, float* da2, float* dz2, float* dz1,
     float* w2t_stack, float* w2rot_stack, float* slab,
     int* yb, unsigned char* pidx, unsigned char* m2, unsigned char* m3,
-    double* acc2k,
+    double* acc2k,                      // 2K doubles; 3K when mu > 0
     const float* lr_t, float max_norm, float p1, float p2,
-    float* stats_out, float* loss_out, hipStream_t s, int use_bf16);
+    float* stats_out, float* loss_out, hipStream_t s, int use_bf16,
+    float mu);
 void launch_mega_clip_sgd(float* params_stack, float* grads_stack,
                           long long P, int K, double* acc2k, float max_norm,
-                          const float* lr_t, float* stats_out, hipStream_t s);
+                          const float* lr_t, float* stats_out, hipStream_t s,
+                          const float* server, float mu,
+                          const unsigned char* active,  // [K] or null = all
+                          float* loss_out);             // [K] or null
 void launch_mega_pseudo_accum(float* grads_stack, const float* server,
                               const float* params_stack,
                               const float* weights_dev, float* round_accum,

@@ -89,12 +89,21 @@ class FusedCNNEpoch:
         self._order_ev = None
 
     def run_epoch(self, shard_x: torch.Tensor, shard_y: torch.Tensor,
-                  order_cpu: torch.Tensor, lr: float, seed: int):
+                  order_cpu: torch.Tensor, lr: float, seed: int, prox=None):
         """Train one local epoch over the device-resident shard.
+
+        ``prox = (mu, w_global_flat)`` trains FedProx: every step's
+        gradient is ``g + mu (w - w_global)`` before the clip and its loss
+        includes ``0.5 mu ||w - w_global||^2``
+        (``Trainer.run_train_epoch(prox=...)``).
 
         Returns (n_samples, n_batches); loss/stats stay in
         ``self.loss_acc`` / ``self.stats_acc`` (device, no sync).
         """
+        mu, server = (0.0, None) if prox is None else prox
+        mu = float(mu)
+        if mu == 0.0:
+            server = None
         n = shard_y.numel()
         x = shard_x.reshape(n, -1)
         assert x.shape[1] == 784, "fused CNN epoch expects 784-feature rows"
@@ -118,7 +127,7 @@ class FusedCNNEpoch:
                      self.work_f, self.work_i, self.work_b, self.work_d,
                      self.lr_t, self.max_norm, self.p1, self.p2,
                      self.stats_acc, self.loss_acc, int(seed),
-                     self.use_bf16)
+                     self.use_bf16, server=server, mu=mu)
         return n, (n + self.bs - 1) // self.bs
 
 
@@ -129,11 +138,13 @@ class MegaRound:
     blocks fills the 256-CU chip) and the host enqueues ~22 kernels per
     step instead of ~22 per client per step.  fp32 path; per-client
     dropout Philox streams are bit-identical to the per-client fused
-    epoch (client-local indices)."""
+    epoch (client-local indices).  ``mu > 0`` trains FedProx against the
+    server arena (proximal term and regulariser for the clients still
+    active at a step; see csrc/fused_cnn.hip); ``mu = 0`` is FedAvg."""
 
     def __init__(self, arena: ParameterArena, num_classes: int, bs: int,
                  p1: float, p2: float, max_grad_norm, k_cap: int = 32,
-                 use_bf16: bool = False):
+                 use_bf16: bool = False, mu: float = 0.0):
         assert HAS_EXT and arena.device.type == "cuda"
         self.arena = arena
         self.C = int(num_classes)
@@ -142,6 +153,7 @@ class MegaRound:
         self.max_norm = float(max_grad_norm) if max_grad_norm else -1.0
         self.k_cap = int(k_cap)
         self.use_bf16 = bool(use_bf16)
+        self.mu = float(mu)
         self._alloc_k = 0
         dev = arena.device
         self.lr_t = torch.zeros(1, dtype=torch.float32, device=dev)
@@ -165,7 +177,8 @@ class MegaRound:
         self.work_i = torch.empty(G, dtype=torch.int32, device=dev)
         self.work_b = torch.empty(G * (9216 * 2 + 128), dtype=torch.uint8,
                                   device=dev)
-        self.work_d = torch.empty(2 * k, dtype=torch.float64, device=dev)
+        # per client: clip sum, sumsq (+ FedProx: sum (w - w_g)^2)
+        self.work_d = torch.empty(3 * k, dtype=torch.float64, device=dev)
         self.loss_out = torch.zeros(k, dtype=torch.float32, device=dev)
         self.stats_out = torch.zeros(2 * k, dtype=torch.float32, device=dev)
         self._alloc_k = k
@@ -226,6 +239,6 @@ class MegaRound:
             server_arena.data, self.params_stack, self.grads_stack,
             round_accum, self.work_f, self.work_i, self.work_b, self.work_d,
             self.lr_t, self.max_norm, self.p1, self.p2,
-            self.stats_out, self.loss_out, self.use_bf16)
+            self.stats_out, self.loss_out, self.use_bf16, mu=self.mu)
         return round_outputs(client_ids, counts, self.bs, self.loss_out,
                              self.stats_out, self.arena.total)

@@ -22,7 +22,10 @@ accumulate are the K-stacked kernels of csrc/fused_cnn.hip, and the WHOLE
 local epoch is captured as one hipGraph per shape.  Ragged epochs are
 masked by labels: inactive rows get ``PAD_LABEL`` (the loss's
 ignore_index), so they contribute exactly zero loss and gradient and a
-finished client's SGD no-ops.
+finished client's SGD no-ops.  With ``mu > 0`` (FedProx) the clip kernels
+add ``mu (w - w_server)`` to the gradient of the clients ACTIVE at a step
+(any unmasked row) and the regulariser to their loss; a finished client,
+whose weights have left the server's, gets neither and stays put.
 """
 
 from __future__ import annotations
@@ -127,10 +130,12 @@ class GraphedMegaRound:
     EAGER_ENV: str    # set to "1": run the epoch eagerly, never capture
 
     def __init__(self, arena: ParameterArena, bs: int, max_grad_norm,
-                 k_cap: int = 32):
+                 k_cap: int = 32, mu: float = 0.0):
         assert HAS_EXT and arena.device.type == "cuda"
         self.arena = arena
         self.bs = int(bs)
+        # fixed per instance: the captured graphs bake it in
+        self.mu = float(mu)
         self.max_norm = float(max_grad_norm) if max_grad_norm else -1.0
         self.k_cap = int(k_cap)
         self.lr_t = torch.zeros(1, dtype=torch.float32, device=arena.device)
@@ -177,9 +182,11 @@ class GraphedMegaRound:
             "flat": torch.zeros(K, P, device=dev, requires_grad=True),
             "idx": torch.zeros(steps, R, dtype=torch.int64, device=dev),
             "ymask": torch.zeros(steps, R, dtype=torch.bool, device=dev),
+            # FedProx: client k is active at step t (has an unmasked row)
+            "active": torch.zeros(steps, K, dtype=torch.bool, device=dev),
             "loss_dev": torch.zeros(K, device=dev),
             "stats_out": torch.zeros(2 * K, device=dev),
-            "acc2k": torch.zeros(2 * K, dtype=torch.float64, device=dev),
+            "acc2k": torch.zeros(3 * K, dtype=torch.float64, device=dev),
             "weights": torch.zeros(K, device=dev),
             "accum": torch.zeros(P, device=dev),
             "graph": None,
@@ -187,6 +194,7 @@ class GraphedMegaRound:
         }
         x_all, y_all = store.x, store.y
         server = self._server_data
+        mu = self.mu
 
         def epoch_body():
             flat = g["flat"]
@@ -200,9 +208,12 @@ class GraphedMegaRound:
                 loss = self._step(flat, x, y, K, g["loss_dev"])
                 loss.backward()
                 self._after_backward(flat.grad)
+                # mu == 0 ignores the FedProx arguments (plain clip + SGD)
                 _C.mega_clip_sgd(flat.data.reshape(-1),
                                  flat.grad.reshape(-1), K, g["acc2k"],
-                                 self.max_norm, self.lr_t, g["stats_out"])
+                                 self.max_norm, self.lr_t, g["stats_out"],
+                                 server=server, mu=mu, active=g["active"][t],
+                                 loss_out=g["loss_dev"])
             _C.mega_pseudo_accum(flat.grad.reshape(-1), server,
                                  flat.data.reshape(-1), g["weights"],
                                  g["accum"])
@@ -261,6 +272,7 @@ class GraphedMegaRound:
 
         g["idx"].copy_(idx)
         g["ymask"].copy_(mask)
+        g["active"].copy_(mask.view(steps, K, bs).any(dim=2))
         g["weights"].copy_(torch.tensor([float(c) for c in counts]))
         self.lr_t.fill_(float(initial_lr))
         if not g["captured"]:

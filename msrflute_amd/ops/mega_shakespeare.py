@@ -77,8 +77,9 @@ class ShakespeareMegaRound(GraphedMegaRound):
     EAGER_ENV = "MEGA_SHK_EAGER"
 
     def __init__(self, arena: ParameterArena, bs: int,
-                 max_grad_norm, k_cap: int = 32, use_bf16: bool = False):
-        super().__init__(arena, bs, max_grad_norm, k_cap)
+                 max_grad_norm, k_cap: int = 32, use_bf16: bool = False,
+                 mu: float = 0.0):
+        super().__init__(arena, bs, max_grad_norm, k_cap, mu=mu)
         vc = matches_char_lstm(arena)
         assert vc is not None
         self.V, self.E = vc
