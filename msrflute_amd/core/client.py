@@ -27,7 +27,8 @@ from .. import ops
 from ..models import make_model
 from ..ops.arena import ParameterArena
 from ..ops.fused_optim import make_arena_optimizer
-from ..ops.mega_round import lookup_round, plan_round, round_outputs
+from ..ops.mega_round import (DGASpec, lookup_round, plan_round,
+                              round_outputs)
 from ..strategies import select_strategy
 from ..utils import (ScheduledSamplingScheduler, alpha_update, make_optimizer,
                      print_rank, to_device)
@@ -602,11 +603,18 @@ class ClientPool:
         pm = prim.config.get("privacy_metrics_config", None)
         mu = fused_round_mu(prim.config["strategy"], cc, prim.model_config,
                             bool(pm and pm["apply_metrics"]))
-        if mu is None:
+        # DGA runs on the cross-client mega rounds only (its tail forms the
+        # aggregation weights on the device); mu is then FedAvg's
+        dga = fused_round_dga(prim.config) if mu is None else None
+        if mu is None and dga is None:
             return None
+        if dga is not None:
+            mu = 0.0
+            if len(client_ids) > 32:   # the tail's K limit (DGA_MAX_K)
+                return None
         out = self._try_graphed_mega("_mega_lstm", True, _build_mega_lstm,
                                      data_cfg, client_ids, initial_lr, seeds,
-                                     precisions=("bf16",), mu=mu)
+                                     precisions=("bf16",), mu=mu, dga=dga)
         if out is None:
             # OPT-IN: measured SLOWER than the per-client epoch-graph path
             # on ROCm 7.2 — MIOpen decomposes groups=K convs into K
@@ -618,7 +626,7 @@ class ClientPool:
             out = self._try_graphed_mega(
                 "_mega_resnet", cc.get("use_mega_round_resnet", False),
                 _build_mega_resnet, data_cfg, client_ids, initial_lr, seeds,
-                mu=mu)
+                mu=mu, dga=dga)
         if out is not None:
             return out
         fc = prim.fused_cnn
@@ -641,7 +649,7 @@ class ClientPool:
                 from ..ops.fused_cnn import MegaRound
                 self._mega = MegaRound(prim.arena, fc.C, fc.bs, fc.p1, fc.p2,
                                        data_cfg.get("max_grad_norm"),
-                                       use_bf16=fc.use_bf16, mu=mu)
+                                       use_bf16=fc.use_bf16, mu=mu, dga=dga)
             if self._mega.supports(len(client_ids)):
                 out = self._mega.run(store, ds, client_ids, seeds, initial_lr,
                                      self.server_arena, self.round_accums[0],
@@ -649,6 +657,8 @@ class ClientPool:
                 if out is not None:
                     self._mega_round_done(len(client_ids))
                     return out
+        if dga is not None:
+            return None  # _C.cnn_round weights by sample count: the pool
 
         # per-executor fused rounds: each chunk's shuffle orders are drawn
         # right before its launch, so the host work of chunk k+1 overlaps
@@ -674,10 +684,10 @@ class ClientPool:
         return outputs
 
     def _try_graphed_mega(self, attr, enabled, build, data_cfg, client_ids,
-                          initial_lr, seeds, precisions=(), mu=0.0):
+                          initial_lr, seeds, precisions=(), mu=0.0, dga=None):
         """One graph-captured cross-client round
         (ops/mega_round.GraphedMegaRound) when the model being trained is
-        the one ``build(prim, data_cfg, mu)`` recognises (it returns the
+        the one ``build(prim, data_cfg, mu, dga)`` recognises (it returns the
         driver, or None for any other model); the driver is kept in
         ``self.<attr>``.  ``precisions`` lists the ``mixed_precision``
         values the driver implements besides fp32.  Returns outputs or
@@ -699,7 +709,7 @@ class ClientPool:
                 or opt_cfg.get("nesterov", False)):
             return None
         if getattr(self, attr) is None:
-            mega = build(prim, data_cfg, mu) if ops.HAS_EXT else None
+            mega = build(prim, data_cfg, mu, dga) if ops.HAS_EXT else None
             setattr(self, attr, mega or False)
         mega = getattr(self, attr)
         if mega is False or not mega.supports(len(client_ids)):
@@ -722,7 +732,7 @@ class ClientPool:
         prim.perf_acc["clients"] = prim.perf_acc.get("clients", 0) + n_clients
 
 
-def _build_mega_lstm(prim, data_cfg, mu=0.0):
+def _build_mega_lstm(prim, data_cfg, mu=0.0, dga=None):
     """The Shakespeare char-LSTM mega round (ops/mega_shakespeare.py), or
     None if ``prim`` trains another model."""
     from ..ops.mega_shakespeare import ShakespeareMegaRound, matches_char_lstm
@@ -732,10 +742,10 @@ def _build_mega_lstm(prim, data_cfg, mu=0.0):
         prim.arena, data_cfg.get("batch_size", 4),
         data_cfg.get("max_grad_norm"),
         use_bf16=prim.client_config.get("mixed_precision", "") == "bf16",
-        mu=mu)
+        mu=mu, dga=dga)
 
 
-def _build_mega_resnet(prim, data_cfg, mu=0.0):
+def _build_mega_resnet(prim, data_cfg, mu=0.0, dga=None):
     """The fed-CIFAR100 ResNet-18 mega round (ops/mega_resnet.py), or None
     if ``prim`` trains another model (or one without GroupNorm)."""
     from ..ops.mega_resnet import ResNetMegaRound, matches_resnet18
@@ -743,7 +753,8 @@ def _build_mega_resnet(prim, data_cfg, mu=0.0):
     if cpg <= 0 or matches_resnet18(prim.arena) is None:
         return None
     return ResNetMegaRound(prim.arena, data_cfg.get("batch_size", 20),
-                           data_cfg.get("max_grad_norm"), cpg, mu=mu)
+                           data_cfg.get("max_grad_norm"), cpg, mu=mu,
+                           dga=dga)
 
 
 def fused_round_mu(strategy, client_config, model_config=None,
@@ -772,6 +783,61 @@ def fused_round_mu(strategy, client_config, model_config=None,
     if strategy == "FedAvg":
         return 0.0
     return float(client_config.get("mu", 0.001))
+
+
+def fused_round_dga(config):
+    """The DGA gate of the cross-client mega rounds (pure: config in,
+    decision out), next to ``fused_round_mu``.  Returns the ``DGASpec`` the
+    drivers end the round with, or None when the round must take the
+    per-client path (the stream pool).
+
+    The DGA tail forms ``exp(-beta * tw)`` with ``filter_weight`` and the
+    clip-only local-DP rescale on the device and nothing else, so the gate
+    accepts only when ``DGA.generate_client_payload`` would do nothing
+    more: fast aggregation without RL or staleness (the pool's own
+    conditions), no privacy metrics, frozen layer, num_skips_threshold or
+    smoothed-gradient stats, no update quantization (it needs a quantile
+    sort) and local DP either off or clip-only (eps < 0; the noised mode
+    draws host RNG)."""
+    if config.get("strategy") != "DGA":
+        return None
+    sc = config.get("server_config") or {}
+    cc = config.get("client_config") or {}
+    if (not sc.get("fast_aggregation", True) or sc.get("wantRL", False)
+            or float(sc.get("stale_prob", 0.0) or 0.0) != 0.0
+            or config.get("dump_norm_stats", False)
+            or sc.get("type") == "personalization"):
+        return None
+    pm = config.get("privacy_metrics_config", None)
+    if pm and pm.get("apply_metrics", False):
+        return None
+    if (config.get("model_config") or {}).get("freeze_layer", None):
+        return None
+    if int(cc.get("num_skips_threshold", -1)) >= 0:
+        return None
+    if cc.get("stats_on_smooth_grad", False):
+        return None
+    if cc.get("quant_thresh", None) is not None:
+        return None
+    median = sc.get("aggregate_median")
+    if median == "softmax":
+        source = sc.get("weight_train_loss", "train_loss")
+        if source not in ("train_loss", "mag_var_loss", "mag_mean_loss"):
+            source = "mag"  # generate_client_payload's else branch
+        beta = float(sc["softmax_beta"])
+    elif median == "mean":
+        source, beta = "mean", 0.0
+    else:
+        return None
+    dp = config.get("dp_config", None)
+    clip, max_grad = False, 0.0
+    if dp is not None and dp.get("enable_local_dp", False):
+        if not float(dp["eps"]) < 0:
+            return None
+        clip, max_grad = True, float(dp["max_grad"])
+        if not max_grad > 0:
+            return None
+    return DGASpec(source, beta, clip, max_grad)
 
 
 def _fused_round_impl(ex, store, plan, client_ids, seeds, initial_lr,

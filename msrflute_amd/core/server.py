@@ -26,7 +26,8 @@ import torch
 from ..comm.runtime import FedRuntime
 from ..strategies import select_strategy
 from ..utils import log_metric, print_rank, update_json_log
-from .client import Client, ClientExecutor, fused_round_mu
+from .client import (Client, ClientExecutor, fused_round_dga,
+                     fused_round_mu)
 from .evaluation import Evaluation
 from .trainer import (ModelUpdater, Trainer, flush_saves, get_lr,
                       set_component_wise_lr)
@@ -317,11 +318,14 @@ class OptimizationServer:
         fused_outputs = None
         # The fused drivers train plain SGD (FedAvg) or SGD with the exact
         # per-batch proximal term (FedProx); fused_round_mu is the gate.
+        # DGA takes the cross-client mega rounds when fused_round_dga
+        # accepts (weights and clip-only local DP formed on the device).
         if (hasattr(self.executor, "run_fused_round_batch")
-                and fused_round_mu(
+                and (fused_round_mu(
                     self.config["strategy"], self.config["client_config"],
                     self.config.get("model_config"),
                     apply_privacy_metrics) is not None
+                    or fused_round_dga(self.config) is not None)
                 and self.config["client_config"].get("use_fused_round",
                                                      True)):
             seeds = [rt.round_rng(i, salt=100 + c).getrandbits(62)

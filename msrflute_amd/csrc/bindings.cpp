@@ -737,6 +737,27 @@ torch::Tensor dbg_mfma_bf16_probe(torch::Tensor A, torch::Tensor B) {
 // batch-step (fused_cnn.hip).  Caller provides the per-client
 // metadata both on device (kernel use) and host (max_batches), the
 // K*P parameter/gradient stacks and a float workspace sliced here.
+// validates the DGA argument group shared by cnn_round_mega and
+// mega_dga_accum; returns dga_out's pointer (4K doubles)
+static double* dga_check(int64_t mode, double beta, bool clip,
+                         double max_grad,
+                         const c10::optional<torch::Tensor>& dga_out,
+                         int64_t K, DgaArgs* out) {
+  TORCH_CHECK(mode >= DGA_MEAN && mode <= DGA_MAG, "dga_mode out of range");
+  TORCH_CHECK(K > 0 && K <= DGA_MAX_K, "the DGA tail takes K <= ", DGA_MAX_K);
+  TORCH_CHECK(!clip || max_grad > 0.0, "dga clip needs max_grad > 0");
+  TORCH_CHECK(dga_out.has_value() && dga_out->is_cuda() &&
+              dga_out->is_contiguous() &&
+              dga_out->scalar_type() == torch::kFloat64 &&
+              dga_out->numel() >= 4 * K,
+              "dga_out must hold 4K float64 on the device");
+  out->mode = (int)mode;
+  out->clip = clip ? 1 : 0;
+  out->beta = beta;
+  out->max_grad = max_grad;
+  return dga_out->data_ptr<double>();
+}
+
 void cnn_round_mega(torch::Tensor shard_x, torch::Tensor shard_y,
                     torch::Tensor orders_dev, torch::Tensor row_bases_dev,
                     torch::Tensor order_offs_dev, torch::Tensor counts_dev,
@@ -748,8 +769,18 @@ void cnn_round_mega(torch::Tensor shard_x, torch::Tensor shard_y,
                     torch::Tensor work_b, torch::Tensor work_d,
                     torch::Tensor lr_t, double max_norm, double p1,
                     double p2, torch::Tensor stats_out,
-                    torch::Tensor loss_out, bool use_bf16, double mu) {
+                    torch::Tensor loss_out, bool use_bf16, double mu,
+                    int64_t dga_mode, double dga_beta, bool dga_clip,
+                    double dga_max_grad,
+                    c10::optional<torch::Tensor> dga_out) {
   TORCH_CHECK(mu >= 0.0, "mu must be >= 0");
+  // DGA group (dga_mode >= 0): the round ends in the DGA tail
+  DgaArgs dga_args;
+  double* dga_out_p = nullptr;
+  const bool has_dga = dga_mode >= 0;
+  if (has_dga)
+    dga_out_p = dga_check(dga_mode, dga_beta, dga_clip, dga_max_grad,
+                          dga_out, counts_host.numel(), &dga_args);
   check_flat(server_params, "server_params");
   check_flat(params_stack, "params_stack");
   check_flat(grads_stack, "grads_stack");
@@ -831,7 +862,8 @@ void cnn_round_mega(torch::Tensor shard_x, torch::Tensor shard_y,
       work_i.data_ptr<int>(), pidx, m2, m3, work_d.data_ptr<double>(),
       lr_t.data_ptr<float>(), (float)max_norm, (float)p1, (float)p2,
       stats_out.data_ptr<float>(), loss_out.data_ptr<float>(),
-      cur_stream(), use_bf16 ? 1 : 0, (float)mu);
+      cur_stream(), use_bf16 ? 1 : 0, (float)mu,
+      has_dga ? &dga_args : nullptr, dga_out_p);
 }
 
 // per-client clip + sufficient stats + SGD over a K-stacked flat arena
@@ -895,6 +927,36 @@ void mega_pseudo_accum(torch::Tensor grads_stack, torch::Tensor server,
                            cur_stream());
 }
 
+// DGA end-of-round tail over a K-stacked flat arena (graph-capture safe:
+// no host sync, no allocation): softmax weight and clip-only local DP
+// formed on the device, accumulated into ``accum``; dga_out[4K] f64 =
+// weight_k, norm_k, c_k, scratch
+void mega_dga_accum(torch::Tensor params_stack, torch::Tensor server,
+                    int64_t K, torch::Tensor loss, torch::Tensor stats,
+                    torch::Tensor counts, int64_t bs, int64_t dga_mode,
+                    double dga_beta, bool dga_clip, double dga_max_grad,
+                    torch::Tensor accum, torch::Tensor dga_out) {
+  check_flat(params_stack, "params_stack"); check_flat(server, "server");
+  check_flat(loss, "loss"); check_flat(stats, "stats");
+  check_flat(accum, "accum");
+  long long P = server.numel();
+  TORCH_CHECK(P > 0 && K > 0 && params_stack.numel() == K * P &&
+              accum.numel() == P, "stack / server / accum sizes disagree");
+  TORCH_CHECK(loss.numel() >= K && stats.numel() >= 2 * K);
+  TORCH_CHECK(counts.is_cuda() && counts.is_contiguous() &&
+              counts.scalar_type() == torch::kInt64 && counts.numel() >= K,
+              "counts must be K int64 on the device");
+  TORCH_CHECK(bs >= 1);
+  DgaArgs a;
+  double* out = dga_check(dga_mode, dga_beta, dga_clip, dga_max_grad,
+                          dga_out, K, &a);
+  launch_mega_dga_accum(
+      params_stack.data_ptr<float>(), server.data_ptr<float>(), P, (int)K,
+      loss.data_ptr<float>(), stats.data_ptr<float>(),
+      reinterpret_cast<const long long*>(counts.data_ptr<int64_t>()),
+      (int)bs, a, accum.data_ptr<float>(), out, cur_stream());
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   // output rows per block of the f32 conv2 forward (its slab seams)
   m.attr("CONV2_FWD_SLAB_ROWS") = CONV2_FWD_SLAB_ROWS;
@@ -903,7 +965,22 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("cnn_round_mega", &cnn_round_mega,
         py::arg("shard_x"), py::arg("shard_y"), py::arg("orders_dev"),
         py::arg("row_bases_dev"), py::arg("order_offs_dev"), py::arg("counts_dev"), py::arg("counts_host"), py::arg("weights_dev"), py::arg("seeds_dev"), py::arg("bs"), py::arg("C"), py::arg("server_params"), py::arg("params_stack"), py::arg("grads_stack"), py::arg("round_accum"), py::arg("work_f"), py::arg("work_i"), py::arg("work_b"), py::arg("work_d"), py::arg("lr_t"), py::arg("max_norm"), py::arg("p1"), py::arg("p2"), py::arg("stats_out"), py::arg("loss_out"), py::arg("use_bf16"),
-        py::arg("mu") = 0.0);
+        py::arg("mu") = 0.0,
+        // DGA group: dga_mode < 0 = absent (the FedAvg / FedProx tail)
+        py::arg("dga_mode") = -1, py::arg("dga_beta") = 0.0,
+        py::arg("dga_clip") = false, py::arg("dga_max_grad") = 0.0,
+        py::arg("dga_out") = py::none());
+  m.def("mega_dga_accum", &mega_dga_accum,
+        py::arg("params_stack"), py::arg("server"), py::arg("K"),
+        py::arg("loss"), py::arg("stats"), py::arg("counts"), py::arg("bs"),
+        py::arg("dga_mode"), py::arg("dga_beta"), py::arg("dga_clip"),
+        py::arg("dga_max_grad"), py::arg("accum"), py::arg("dga_out"));
+  m.attr("DGA_MODES") = py::dict(
+      py::arg("mean") = (int)DGA_MEAN,
+      py::arg("train_loss") = (int)DGA_TRAIN_LOSS,
+      py::arg("mag_var_loss") = (int)DGA_MAG_VAR,
+      py::arg("mag_mean_loss") = (int)DGA_MAG_MEAN,
+      py::arg("mag") = (int)DGA_MAG);
   m.def("mega_clip_sgd", &mega_clip_sgd,
         py::arg("params_stack"), py::arg("grads_stack"), py::arg("K"), py::arg("acc2k"), py::arg("max_norm"), py::arg("lr_t"), py::arg("stats_out"),
         py::arg("server") = py::none(), py::arg("mu") = 0.0,

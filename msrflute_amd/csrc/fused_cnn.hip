@@ -1609,6 +1609,150 @@ __global__ void k_accum_mb(float* __restrict__ round_accum,
 }
 
 // ---------------------------------------------------------------------------
+// DGA tail: the end of a round under dynamic gradient aggregation
+// (strategies/dga.py generate_client_payload, clip-only local DP), with
+// the aggregation weight formed on the device and no K*P pseudo-gradient
+// stack.  Two kernels:
+//   k_dga_normsq_mb (clip only): normsq[k] = sum_p (w_g[p] - w_k[p])^2 in
+//     f64, k_sumsq_mb's reduction (4 chains per thread, shuffle, LDS, one
+//     atomicAdd per (client, chunk) block);
+//   k_dga_accum_mb: every block recomputes the K <= 32 coefficients
+//     c_k = (float)(weight_k * dp_k) into LDS (one thread per client, all
+//     f64), then round_accum[p] += sum_k c_k * (w_g[p] - w_k[p]) with k
+//     ascending: one __fsub_rn, one __fmul_rn and one __fadd_rn per
+//     (k, p), the roundings of k_pseudo_grad_mb + k_accum_mb.  A client
+//     with c_k == 0 is skipped, so it leaves round_accum's bits alone (the
+//     host does not accumulate a zero-weight client either).
+// ---------------------------------------------------------------------------
+#define DGA_MIN_WEIGHT 1e-7  // strategies/dga.py MIN_WEIGHT
+
+__global__ void k_dga_normsq_mb(const float* __restrict__ params,
+                                const float* __restrict__ server,
+                                long long P, int blocks_per_k,
+                                double* __restrict__ normsq) {
+  int k = blockIdx.x / blocks_per_k;
+  int c = blockIdx.x % blocks_per_k;
+  long long lo = (long long)c * SUMSQ_CHUNK;
+  long long hi = lo + SUMSQ_CHUNK;
+  if (hi > P) hi = P;
+  const float* w = params + (long long)k * P;
+  double r0 = 0.0, r1 = 0.0, r2 = 0.0, r3 = 0.0;
+  long long i = lo + (long long)threadIdx.x * 4;
+  for (; i + 3 < hi; i += (long long)blockDim.x * 4) {
+    float d0 = __fsub_rn(server[i], w[i]);
+    float d1 = __fsub_rn(server[i + 1], w[i + 1]);
+    float d2 = __fsub_rn(server[i + 2], w[i + 2]);
+    float d3 = __fsub_rn(server[i + 3], w[i + 3]);
+    r0 += (double)d0 * d0; r1 += (double)d1 * d1;
+    r2 += (double)d2 * d2; r3 += (double)d3 * d3;
+  }
+  for (long long j = i; j < hi; ++j) {  // ragged tail (P % 4)
+    float dj = __fsub_rn(server[j], w[j]);
+    r0 += (double)dj * dj;
+  }
+  double fr = (r0 + r1) + (r2 + r3);
+  for (int d = 32; d > 0; d >>= 1) fr += __shfl_down(fr, d, 64);
+  __shared__ double lds[4];
+  int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  if (lane == 0) lds[wave] = fr;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double tr = 0.0;
+    for (int wv = 0; wv < (int)blockDim.x / 64; ++wv) tr += lds[wv];
+    atomicAdd(normsq + k, tr);
+  }
+}
+
+// weight_k of generate_client_payload, all in f64 as on the host
+__device__ __forceinline__ double dga_weight(const DgaArgs& a, double loss,
+                                             double s, double q,
+                                             long long count, long long n) {
+  if (a.mode == DGA_MEAN) return 1.0;
+  double nd = (double)(n > 1 ? n : 1);
+  double tw;
+  if (a.mode == DGA_TRAIN_LOSS) {
+    tw = loss / (double)(count > 1 ? count : 1);
+  } else if (a.mode == DGA_MAG_VAR) {
+    double mean = s / nd;
+    tw = fmax(__dsub_rn(q / nd, __dmul_rn(mean, mean)), 0.0);
+  } else if (a.mode == DGA_MAG_MEAN) {
+    tw = s / nd;
+  } else {
+    tw = sqrt(fmax(q / nd, 0.0));
+  }
+  double arg = __dmul_rn(-a.beta, tw);
+  double w = exp(arg);
+  // math.exp raises OverflowError (-> MIN_WEIGHT) for a finite argument
+  // only; exp(+inf) returns inf and filter_weight zeroes it
+  if (isinf(w) && !isinf(arg)) w = DGA_MIN_WEIGHT;
+  if (isnan(w) || isinf(w)) w = 0.0;   // filter_weight
+  else if (w > 100.0) w = 100.0;
+  return w;
+}
+
+__global__ void k_dga_accum_mb(float* __restrict__ round_accum,
+                               const float* __restrict__ server,
+                               const float* __restrict__ params, long long P,
+                               int K, const float* __restrict__ loss_out,
+                               const float* __restrict__ stats_out,
+                               const long long* __restrict__ counts, int bs,
+                               DgaArgs a, const double* __restrict__ normsq,
+                               double* __restrict__ dga_out) {
+  __shared__ float coef[DGA_MAX_K];
+  if ((int)threadIdx.x < K) {
+    int k = threadIdx.x;
+    long long cnt = counts[k];
+    long long n = ((cnt + bs - 1) / bs) * P;
+    double w = dga_weight(a, (double)loss_out[k], (double)stats_out[2 * k],
+                          (double)stats_out[2 * k + 1], cnt, n);
+    double norm = 0.0, dp = 1.0;
+    if (a.clip) {
+      norm = sqrt(normsq[k]);
+      if (norm > a.max_grad) dp = a.max_grad / norm;
+    }
+    double c = __dmul_rn(w, dp);
+    coef[k] = (float)c;
+    if (blockIdx.x == 0) {
+      dga_out[k] = w;
+      dga_out[K + k] = norm;
+      dga_out[2 * K + k] = (double)coef[k];  // as applied: f32-rounded
+    }
+  }
+  __syncthreads();
+  for (long long p = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+       p < P; p += (long long)gridDim.x * blockDim.x) {
+    float wg = server[p];
+    float s = round_accum[p];
+    for (int k = 0; k < K; ++k) {
+      float c = coef[k];
+      if (c != 0.f) {  // block-uniform: coef is per client
+        float d = __fsub_rn(wg, params[(long long)k * P + p]);
+        s = __fadd_rn(s, __fmul_rn(c, d));
+      }
+    }
+    round_accum[p] = s;
+  }
+}
+
+static void dga_tail(const float* params_stack, const float* server,
+                     long long P, int K, const float* loss_out,
+                     const float* stats_out, const long long* counts_dev,
+                     int bs, const DgaArgs& dga, float* round_accum,
+                     double* dga_out, hipStream_t s) {
+  double* normsq = dga_out + 3 * K;
+  if (dga.clip) {
+    int blocks_per_k = (int)((P + SUMSQ_CHUNK - 1) / SUMSQ_CHUNK);
+    hipMemsetAsync(normsq, 0, K * sizeof(double), s);
+    hipLaunchKernelGGL(k_dga_normsq_mb, dim3(K * blocks_per_k), dim3(FBLK),
+                       0, s, params_stack, server, P, blocks_per_k, normsq);
+  }
+  int gp = (int)((P + FBLK - 1) / FBLK); if (gp > 2048) gp = 2048;
+  hipLaunchKernelGGL(k_dga_accum_mb, dim3(gp), dim3(FBLK), 0, s, round_accum,
+                     server, params_stack, P, K, loss_out, stats_out,
+                     counts_dev, bs, dga, normsq, dga_out);
+}
+
+// ---------------------------------------------------------------------------
 // bf16 GEMM kernels (mixed precision: bf16 MFMA inputs at ~13-16x the
 // f32 MFMA rate, fp32 accumulators, fp32 master weights/outputs — the
 // SGD step, clip/stats, DP/quant hooks all stay fp32).  The GEMM
@@ -2094,7 +2238,7 @@ extern "C" void launch_cnn_round_mega(
     double* acc2k,
     const float* lr_t, float max_norm, float p1, float p2,
     float* stats_out, float* loss_out, hipStream_t s, int use_bf16,
-    float mu) {
+    float mu, const DgaArgs* dga, double* dga_out) {
   CnnOffsets o = cnn_offsets(C);
   long long P = o.total;
   int G = K * bs;
@@ -2215,6 +2359,11 @@ extern "C" void launch_cnn_round_mega(
                        0, s, params_stack, grads_stack, P, K, acc2k, max_norm,
                        1e-6f, lr_t, stats_out, NoProx{});
   }
+  if (dga) {
+    dga_tail(params_stack, server_params, P, K, loss_out, stats_out,
+             counts_dev, bs, *dga, round_accum, dga_out, s);
+    return;
+  }
   hipLaunchKernelGGL(k_pseudo_grad_mb, dim3(gkp), dim3(FBLK), 0, s,
                      grads_stack, server_params, params_stack, weights_dev,
                      P, K);
@@ -2272,6 +2421,17 @@ extern "C" void launch_mega_pseudo_accum(float* grads_stack,
                      grads_stack, server, params_stack, weights_dev, P, K);
   hipLaunchKernelGGL(k_accum_mb, dim3(gp), dim3(FBLK), 0, s,
                      round_accum, grads_stack, P, K);
+}
+
+extern "C" void launch_mega_dga_accum(const float* params_stack,
+                                      const float* server, long long P, int K,
+                                      const float* loss_out,
+                                      const float* stats_out,
+                                      const long long* counts_dev, int bs,
+                                      DgaArgs dga, float* round_accum,
+                                      double* dga_out, hipStream_t s) {
+  dga_tail(params_stack, server, P, K, loss_out, stats_out, counts_dev, bs,
+           dga, round_accum, dga_out, s);
 }
 
 // ---------------------------------------------------------------------------

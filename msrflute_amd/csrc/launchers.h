@@ -42,6 +42,20 @@ struct CnnWorkspace {
   double *red_partials, *red_acc;
 };
 
+// DGA end-of-round tail (k_dga_normsq_mb / k_dga_accum_mb): how client
+// k's aggregation weight is formed on the device.  ``mode`` selects
+// server_config.weight_train_loss; DGA_MEAN is aggregate_median: mean
+// (weight 1).  ``clip`` is local DP in clip-only mode (eps < 0).
+enum DgaMode { DGA_MEAN = 0, DGA_TRAIN_LOSS = 1, DGA_MAG_VAR = 2,
+               DGA_MAG_MEAN = 3, DGA_MAG = 4 };
+#define DGA_MAX_K 32
+struct DgaArgs {
+  int mode;
+  int clip;
+  double beta;      // softmax_beta
+  double max_grad;  // dp_config.max_grad (clip only)
+};
+
 extern "C" {
 
 // flat_ops.hip
@@ -154,7 +168,11 @@ void launch_cnn_round_mega(
     double* acc2k,                      // 2K doubles; 3K when mu > 0
     const float* lr_t, float max_norm, float p1, float p2,
     float* stats_out, float* loss_out, hipStream_t s, int use_bf16,
-    float mu);
+    float mu,
+    // null: end in k_pseudo_grad_mb + k_accum_mb with weights_dev (the
+    // FedAvg / FedProx launches); else end in the DGA tail, which ignores
+    // weights_dev and writes dga_out (4K doubles, see launch_mega_dga_accum)
+    const DgaArgs* dga, double* dga_out);
 void launch_mega_clip_sgd(float* params_stack, float* grads_stack,
                           long long P, int K, double* acc2k, float max_norm,
                           const float* lr_t, float* stats_out, hipStream_t s,
@@ -165,6 +183,19 @@ void launch_mega_pseudo_accum(float* grads_stack, const float* server,
                               const float* params_stack,
                               const float* weights_dev, float* round_accum,
                               long long P, int K, hipStream_t s);
+
+// DGA tail over a K-stacked flat arena, K <= DGA_MAX_K:
+// round_accum[p] += sum_k c_k (server[p] - params[k*P + p]) with c_k formed
+// on the device from loss_out[K], stats_out[2K] and counts_dev[K].
+// dga_out holds 4K doubles: weight_k, norm_k (0 without clip), c_k, and K
+// doubles of scratch (the clip pass's sum of squares).  No host sync, no
+// allocation: graph-capturable.
+void launch_mega_dga_accum(const float* params_stack, const float* server,
+                           long long P, int K, const float* loss_out,
+                           const float* stats_out,
+                           const long long* counts_dev, int bs, DgaArgs dga,
+                           float* round_accum, double* dga_out,
+                           hipStream_t s);
 
 // fused_cnn.hip — per-kernel debug launchers.  Every operand is a
 // K-stack (client k's rows are [k*bs, (k+1)*bs), its weights / biases /

@@ -140,11 +140,15 @@ class MegaRound:
     dropout Philox streams are bit-identical to the per-client fused
     epoch (client-local indices).  ``mu > 0`` trains FedProx against the
     server arena (proximal term and regulariser for the clients still
-    active at a step; see csrc/fused_cnn.hip); ``mu = 0`` is FedAvg."""
+    active at a step; see csrc/fused_cnn.hip); ``mu = 0`` is FedAvg.
+    With ``dga`` (a ``mega_round.DGASpec``) the call ends in the DGA tail
+    instead of the weighted pseudo-gradient pair: softmax weights and the
+    clip-only local-DP rescale are formed on the device, and ``run``
+    reports them after one [K] read."""
 
     def __init__(self, arena: ParameterArena, num_classes: int, bs: int,
                  p1: float, p2: float, max_grad_norm, k_cap: int = 32,
-                 use_bf16: bool = False, mu: float = 0.0):
+                 use_bf16: bool = False, mu: float = 0.0, dga=None):
         assert HAS_EXT and arena.device.type == "cuda"
         self.arena = arena
         self.C = int(num_classes)
@@ -154,6 +158,8 @@ class MegaRound:
         self.k_cap = int(k_cap)
         self.use_bf16 = bool(use_bf16)
         self.mu = float(mu)
+        self.dga = dga
+        self.calls = 0  # rounds this driver ran
         self._alloc_k = 0
         dev = arena.device
         self.lr_t = torch.zeros(1, dtype=torch.float32, device=dev)
@@ -181,6 +187,8 @@ class MegaRound:
         self.work_d = torch.empty(3 * k, dtype=torch.float64, device=dev)
         self.loss_out = torch.zeros(k, dtype=torch.float32, device=dev)
         self.stats_out = torch.zeros(2 * k, dtype=torch.float32, device=dev)
+        # DGA tail: K x {weight, norm, c, clip scratch}
+        self.dga_out = torch.zeros(4 * k, dtype=torch.float64, device=dev)
         self._alloc_k = k
 
     def supports(self, K: int) -> bool:
@@ -239,6 +247,12 @@ class MegaRound:
             server_arena.data, self.params_stack, self.grads_stack,
             round_accum, self.work_f, self.work_i, self.work_b, self.work_d,
             self.lr_t, self.max_norm, self.p1, self.p2,
-            self.stats_out, self.loss_out, self.use_bf16, mu=self.mu)
+            self.stats_out, self.loss_out, self.use_bf16, mu=self.mu,
+            **(self.dga.kwargs(self.dga_out[:4 * K]) if self.dga else {}))
+        self.calls += 1
+        weights = None
+        if self.dga is not None:
+            # the round's one [K] read, after its launches are queued
+            weights = self.dga_out[:K].tolist()
         return round_outputs(client_ids, counts, self.bs, self.loss_out,
-                             self.stats_out, self.arena.total)
+                             self.stats_out, self.arena.total, weights)

@@ -76,9 +76,9 @@ class ResNetMegaRound(GraphedMegaRound):
     EAGER_ENV = "MEGA_RESNET_EAGER"
 
     def __init__(self, arena: ParameterArena, bs: int, max_grad_norm,
-                 cpg: int, k_cap: int = 32, mu: float = 0.0):
+                 cpg: int, k_cap: int = 32, mu: float = 0.0, dga=None):
         assert cpg > 0
-        super().__init__(arena, bs, max_grad_norm, k_cap, mu=mu)
+        super().__init__(arena, bs, max_grad_norm, k_cap, mu=mu, dga=dga)
         self.cpg = int(cpg)
         nc = matches_resnet18(arena)
         assert nc is not None

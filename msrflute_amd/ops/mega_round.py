@@ -26,18 +26,48 @@ finished client's SGD no-ops.  With ``mu > 0`` (FedProx) the clip kernels
 add ``mu (w - w_server)`` to the gradient of the clients ACTIVE at a step
 (any unmasked row) and the regulariser to their loss; a finished client,
 whose weights have left the server's, gets neither and stays put.
+
+With a ``DGASpec`` the round ends in the DGA tail (``_C.mega_dga_accum``,
+or the same kernels inside ``_C.cnn_round_mega``): the softmax
+aggregation weight and the clip-only local-DP rescale are formed on the
+device from the loss and stats the round already holds, and the drivers
+report the weights through one [K] read per round.
 """
 
 from __future__ import annotations
 
 import os
 import time
-from typing import Dict, Tuple
+from typing import Dict, NamedTuple, Optional, Tuple
 
 import torch
 
 from . import HAS_EXT, _C
 from .arena import ParameterArena
+
+
+# weight sources of the DGA tail -> DgaMode of csrc/launchers.h
+# (== _C.DGA_MODES); "mean" is aggregate_median: mean, the rest are
+# server_config.weight_train_loss under aggregate_median: softmax
+DGA_MODES = {"mean": 0, "train_loss": 1, "mag_var_loss": 2,
+             "mag_mean_loss": 3, "mag": 4}
+
+
+class DGASpec(NamedTuple):
+    """What the DGA tail needs (core.client.fused_round_dga builds it)."""
+    source: str            # a key of DGA_MODES
+    beta: float            # softmax_beta
+    clip: bool = False     # local DP, clip-only mode
+    max_grad: float = 0.0  # dp_config.max_grad
+
+    def kwargs(self, dga_out=None):
+        """The DGA argument group of the bindings."""
+        kw = dict(dga_mode=DGA_MODES[self.source], dga_beta=float(self.beta),
+                  dga_clip=bool(self.clip),
+                  dga_max_grad=float(self.max_grad))
+        if dga_out is not None:
+            kw["dga_out"] = dga_out
+        return kw
 
 
 def lookup_round(store, user_list, client_ids, desired_max_samples=None):
@@ -96,12 +126,16 @@ def batch_indices(counts, row_lo, orders, bs):
     return idx, mask
 
 
-def round_outputs(client_ids, counts, bs, loss_dev, stats_dev, arena_total):
+def round_outputs(client_ids, counts, bs, loss_dev, stats_dev, arena_total,
+                  weights=None):
     """Per-client result dicts of a whole-round driver.  Loss and
     sufficient stats stay on the device: ``_lazy`` = (client k's summed
     batch loss, its {sum, sumsq} slice, number of gradient elements the
-    stats cover)."""
+    stats cover).  ``weights``: the aggregation weights (host floats) when
+    they are not the sample counts (DGA)."""
     now = time.time()
+    if weights is None:
+        weights = [float(c) for c in counts]
     outputs = []
     for k, cid in enumerate(client_ids):
         nb = (counts[k] + bs - 1) // bs
@@ -109,7 +143,7 @@ def round_outputs(client_ids, counts, bs, loss_dev, stats_dev, arena_total):
             "cs": {"setup": 0.0, "training": 0.0, "full cost": 0.0,
                    "dataloader": 0.0},
             "ns": counts[k],
-            "pl": {"weight": float(counts[k]), "grad": None,
+            "pl": {"weight": float(weights[k]), "grad": None,
                    "pooled": True},
             "_lazy": (loss_dev[k].reshape(()),
                       stats_dev[2 * k:2 * k + 2],
@@ -130,12 +164,15 @@ class GraphedMegaRound:
     EAGER_ENV: str    # set to "1": run the epoch eagerly, never capture
 
     def __init__(self, arena: ParameterArena, bs: int, max_grad_norm,
-                 k_cap: int = 32, mu: float = 0.0):
+                 k_cap: int = 32, mu: float = 0.0,
+                 dga: Optional[DGASpec] = None):
         assert HAS_EXT and arena.device.type == "cuda"
         self.arena = arena
         self.bs = int(bs)
-        # fixed per instance: the captured graphs bake it in
+        # fixed per instance: the captured graphs bake them in
         self.mu = float(mu)
+        self.dga = dga
+        self.calls = 0  # rounds this driver ran
         self.max_norm = float(max_grad_norm) if max_grad_norm else -1.0
         self.k_cap = int(k_cap)
         self.lr_t = torch.zeros(1, dtype=torch.float32, device=arena.device)
@@ -188,6 +225,9 @@ class GraphedMegaRound:
             "stats_out": torch.zeros(2 * K, device=dev),
             "acc2k": torch.zeros(3 * K, dtype=torch.float64, device=dev),
             "weights": torch.zeros(K, device=dev),
+            # DGA tail: sample counts in, {weight, norm, c, scratch} out
+            "counts": torch.zeros(K, dtype=torch.int64, device=dev),
+            "dga_out": torch.zeros(4 * K, dtype=torch.float64, device=dev),
             "accum": torch.zeros(P, device=dev),
             "graph": None,
             "captured": False,
@@ -195,6 +235,7 @@ class GraphedMegaRound:
         x_all, y_all = store.x, store.y
         server = self._server_data
         mu = self.mu
+        dga = self.dga
 
         def epoch_body():
             flat = g["flat"]
@@ -214,6 +255,12 @@ class GraphedMegaRound:
                                  self.max_norm, self.lr_t, g["stats_out"],
                                  server=server, mu=mu, active=g["active"][t],
                                  loss_out=g["loss_dev"])
+            if dga is not None:
+                _C.mega_dga_accum(flat.data.reshape(-1), server, K,
+                                  g["loss_dev"], g["stats_out"], g["counts"],
+                                  self.bs, accum=g["accum"],
+                                  **dga.kwargs(g["dga_out"]))
+                return
             _C.mega_pseudo_accum(flat.grad.reshape(-1), server,
                                  flat.data.reshape(-1), g["weights"],
                                  g["accum"])
@@ -274,6 +321,7 @@ class GraphedMegaRound:
         g["ymask"].copy_(mask)
         g["active"].copy_(mask.view(steps, K, bs).any(dim=2))
         g["weights"].copy_(torch.tensor([float(c) for c in counts]))
+        g["counts"].copy_(torch.tensor(counts, dtype=torch.int64))
         self.lr_t.fill_(float(initial_lr))
         if not g["captured"]:
             # first use of this shape: capture on THIS round's real data
@@ -289,5 +337,10 @@ class GraphedMegaRound:
             g["graph"].replay()
         # fold the epoch's accumulated weighted pseudo-gradients
         round_accum += g["accum"]
+        self.calls += 1
+        weights = None
+        if self.dga is not None:
+            # the round's one [K] read, after its launches are queued
+            weights = g["dga_out"][:K].tolist()
         return round_outputs(client_ids, counts, bs, g["loss_dev"],
-                             g["stats_out"], self.arena.total)
+                             g["stats_out"], self.arena.total, weights)

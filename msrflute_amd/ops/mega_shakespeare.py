@@ -78,8 +78,8 @@ class ShakespeareMegaRound(GraphedMegaRound):
 
     def __init__(self, arena: ParameterArena, bs: int,
                  max_grad_norm, k_cap: int = 32, use_bf16: bool = False,
-                 mu: float = 0.0):
-        super().__init__(arena, bs, max_grad_norm, k_cap, mu=mu)
+                 mu: float = 0.0, dga=None):
+        super().__init__(arena, bs, max_grad_norm, k_cap, mu=mu, dga=dga)
         vc = matches_char_lstm(arena)
         assert vc is not None
         self.V, self.E = vc
