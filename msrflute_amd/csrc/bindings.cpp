@@ -172,43 +172,90 @@ void quant_bin_mask(torch::Tensor x, torch::Tensor min_t, torch::Tensor max_t,
                         thresh_t.data_ptr<float>(), (int)n_bins, cur_stream());
 }
 
-// the ONE slicer that lays the per-client CNN workspace out inside the
-// caller's buffers (cnn_epoch and cnn_round share it)
+// the ONE slicer of the CNN workspace (G = K * bs rows over K clients;
+// K = 1 for cnn_epoch / cnn_round).  Byte layout: pidx at 0, m2 at G*9216,
+// m3 at 2*G*9216.  The float layout may be reordered on two conditions:
+// dlogits stays last (G*C need not be a multiple of 4 floats), and every
+// region before it stays a multiple of 4 floats, so that the buffers the
+// kernels move as float4 keep their 16 B alignment.
 static CnnWorkspace slice_ws(torch::Tensor& work_f, torch::Tensor& work_i,
-                             torch::Tensor& work_b, torch::Tensor& work_d,
-                             int B, int C) {
+                             torch::Tensor& work_b, long long G, long long K,
+                             long long C) {
+  CnnWorkspaceSizes z = cnn_workspace_sizes(G, K, C);
+  TORCH_CHECK(work_f.numel() >= z.n_float, "float workspace too small");
+  TORCH_CHECK(work_i.numel() >= z.n_int, "int workspace too small");
+  TORCH_CHECK(work_b.numel() >= z.n_byte, "byte workspace too small");
   float* f = work_f.data_ptr<float>();
+  auto take = [&](long long n) { float* p = f; f += n; return p; };
   CnnWorkspace ws;
-  ws.xb = f;            f += (long long)B * 784;
-  ws.a1 = f;            f += (long long)B * 21632;
-  ws.r2 = f;            f += (long long)B * 36864;
-  ws.a2 = f;            f += (long long)B * 9216;
-  ws.z3 = f;            f += (long long)B * 128;
-  ws.a3 = f;            f += (long long)B * 128;
-  ws.dz3 = f;           f += (long long)B * 128;
-  ws.da2 = f;           f += (long long)B * 9216;
-  ws.dz2 = f;           f += (long long)B * 36864;
-  ws.dz1 = f;           f += (long long)B * 21632;
-  ws.wsl = f;           f += (long long)B * 18432;  // split-K partial slab
-  ws.w2t = f;           f += 18432;
-  ws.w2rot = f;         f += 18432;
-  // B*C need not be a multiple of 4 floats: dlogits goes last so that the
-  // buffers the conv2 kernels move as float4 stay 16 B aligned
-  ws.dlogits = f;       f += (long long)B * C;
-  TORCH_CHECK(f - work_f.data_ptr<float>() <= work_f.numel(),
-              "float workspace too small");
-  TORCH_CHECK(work_i.numel() >= B, "int workspace too small");
-  TORCH_CHECK(work_d.numel() >= 2 * 2048 + 2, "double workspace too small");
+  ws.xb = take(G * 784);
+  ws.a1 = take(G * 21632);
+  ws.r2 = take(G * 36864);
+  ws.a2 = take(G * 9216);
+  ws.z3 = take(G * 128);
+  ws.a3 = take(G * 128);
+  ws.dz3 = take(G * 128);
+  ws.da2 = take(G * 9216);
+  ws.dz2 = take(G * 36864);
+  ws.dz1 = take(G * 21632);
+  ws.w2t = take(K * 18432);
+  ws.w2rot = take(K * 18432);
+  ws.wsl = take(G * 18432);
+  ws.dlogits = take(G * C);
+  TORCH_CHECK(f - work_f.data_ptr<float>() == z.n_float,
+              "cnn_workspace_sizes disagrees with the slicer");
   ws.yb = work_i.data_ptr<int>();
   unsigned char* u = work_b.data_ptr<unsigned char>();
-  ws.pidx = u;          u += (long long)B * 9216;
-  ws.m2 = u;            u += (long long)B * 9216;
-  ws.m3 = u;            u += (long long)B * 128;
-  TORCH_CHECK(u - work_b.data_ptr<unsigned char>() <= work_b.numel(),
-              "byte workspace too small");
+  ws.pidx = u;
+  ws.m2 = u + G * 9216;
+  ws.m3 = u + 2 * G * 9216;
+  ws.red_partials = ws.red_acc = nullptr;
+  return ws;
+}
+
+// the K = 1 drivers' double workspace: launch_sum_sumsq2's partials and,
+// in the last two slots, its result
+static void slice_red(CnnWorkspace& ws, torch::Tensor& work_d) {
+  TORCH_CHECK(work_d.numel() >= 2 * 2048 + 2, "double workspace too small");
   ws.red_partials = work_d.data_ptr<double>();
   ws.red_acc = work_d.data_ptr<double>() + work_d.numel() - 2;
-  return ws;
+}
+
+static std::tuple<int64_t, int64_t, int64_t> cnn_workspace_sizes_py(
+    int64_t G, int64_t K, int64_t C) {
+  TORCH_CHECK(G >= K && K >= 1 && C >= 1);
+  CnnWorkspaceSizes z = cnn_workspace_sizes(G, K, C);
+  return {z.n_float, z.n_int, z.n_byte};
+}
+
+// bound every per-client (row_base, order_off, count) against the shard /
+// order tensors so inconsistent host metadata raises instead of launching
+// out-of-bounds device reads.  The three are host int64 tensors of K.
+static void check_client_meta(const torch::Tensor& shard_x,
+                              const torch::Tensor& shard_y,
+                              const torch::Tensor& orders_dev,
+                              const torch::Tensor& row_bases,
+                              const torch::Tensor& order_offs,
+                              const torch::Tensor& counts,
+                              bool allow_empty) {
+  long long n_rows = shard_y.numel();
+  TORCH_CHECK(shard_x.numel() == n_rows * 784,
+              "shard_x rows must match shard_y (784 features each)");
+  long long n_orders = orders_dev.numel();
+  auto rb = row_bases.accessor<int64_t, 1>();
+  auto oo = order_offs.accessor<int64_t, 1>();
+  auto ct = counts.accessor<int64_t, 1>();
+  for (int k = 0; k < (int)counts.numel(); ++k) {
+    TORCH_CHECK(ct[k] >= (allow_empty ? 0 : 1) && rb[k] >= 0 && oo[k] >= 0,
+                "negative per-client metadata",
+                allow_empty ? "" : " or empty client", " at k=", k);
+    TORCH_CHECK(rb[k] + ct[k] <= n_rows,
+                "client ", k, ": row_base+count ", rb[k] + ct[k],
+                " exceeds shard rows ", n_rows);
+    TORCH_CHECK(oo[k] + ct[k] <= n_orders,
+                "client ", k, ": order_off+count ", oo[k] + ct[k],
+                " exceeds orders length ", n_orders);
+  }
 }
 
 // FedProx arguments shared by the CNN / clip entries: mu == 0 is plain
@@ -249,7 +296,8 @@ void cnn_epoch(torch::Tensor shard_x, torch::Tensor shard_y,
   TORCH_CHECK(shard_x.numel() == n * 784, "shard_x must be [n,784]");
   TORCH_CHECK(bs >= 1 && bs <= 32, "fused CNN epoch supports batch <= 32");
   int B = (int)bs;
-  CnnWorkspace ws = slice_ws(work_f, work_i, work_b, work_d, B, (int)C);
+  CnnWorkspace ws = slice_ws(work_f, work_i, work_b, B, 1, C);
+  slice_red(ws, work_d);
   launch_cnn_epoch(shard_x.data_ptr<float>(),
                    reinterpret_cast<const long long*>(
                        shard_y.data_ptr<int64_t>()),
@@ -298,29 +346,10 @@ void cnn_round(torch::Tensor shard_x, torch::Tensor shard_y,
   TORCH_CHECK(row_bases.numel() == K && order_offs.numel() == K &&
               weights.numel() == K && seeds.numel() == K,
               "per-client metadata lengths must all equal K");
-  // bound every per-client (offset, count) against the shard / order
-  // tensors so inconsistent host metadata raises instead of launching
-  // out-of-bounds device reads
-  {
-    long long n_rows = shard_y.numel();
-    TORCH_CHECK(shard_x.numel() == n_rows * 784,
-                "shard_x rows must match shard_y (784 features each)");
-    long long n_orders = orders_dev.numel();
-    auto rb = row_bases.accessor<int64_t, 1>();
-    auto oo = order_offs.accessor<int64_t, 1>();
-    auto ct = counts.accessor<int64_t, 1>();
-    for (int k = 0; k < K; ++k) {
-      TORCH_CHECK(ct[k] >= 0 && rb[k] >= 0 && oo[k] >= 0,
-                  "negative per-client metadata at k=", k);
-      TORCH_CHECK(rb[k] + ct[k] <= n_rows,
-                  "client ", k, ": row_base+count ", rb[k] + ct[k],
-                  " exceeds shard rows ", n_rows);
-      TORCH_CHECK(oo[k] + ct[k] <= n_orders,
-                  "client ", k, ": order_off+count ", oo[k] + ct[k],
-                  " exceeds orders length ", n_orders);
-    }
-  }
-  CnnWorkspace ws = slice_ws(work_f, work_i, work_b, work_d, (int)bs, (int)C);
+  check_client_meta(shard_x, shard_y, orders_dev, row_bases, order_offs,
+                    counts, /*allow_empty=*/true);
+  CnnWorkspace ws = slice_ws(work_f, work_i, work_b, bs, 1, C);
+  slice_red(ws, work_d);
   launch_cnn_round(
       shard_x.data_ptr<float>(),
       reinterpret_cast<const long long*>(shard_y.data_ptr<int64_t>()),
@@ -802,47 +831,13 @@ void cnn_round_mega(torch::Tensor shard_x, torch::Tensor shard_y,
               grads_stack.numel() >= (long long)K * P,
               "parameter stacks too small");
   TORCH_CHECK(stats_out.numel() >= 2 * K && loss_out.numel() >= K);
-  {
-    long long n_rows = shard_y.numel();
-    long long n_orders = orders_dev.numel();
-    auto rb = row_bases_dev.cpu();
-    auto oo = order_offs_dev.cpu();
-    auto rba = rb.accessor<int64_t, 1>();
-    auto ooa = oo.accessor<int64_t, 1>();
-    auto ct = counts_host.accessor<int64_t, 1>();
-    for (int k = 0; k < K; ++k) {
-      TORCH_CHECK(ct[k] > 0 && rba[k] >= 0 && ooa[k] >= 0 &&
-                  rba[k] + ct[k] <= n_rows &&
-                  ooa[k] + ct[k] <= n_orders,
-                  "client ", k, ": metadata out of bounds");
-    }
-  }
-  int G = K * (int)bs;
-  float* f = work_f.data_ptr<float>();
-  auto take = [&](long long n) { float* p = f; f += n; return p; };
-  float* xb = take((long long)G * 784);
-  float* a1 = take((long long)G * 21632);
-  float* r2 = take((long long)G * 36864);
-  float* a2 = take((long long)G * 9216);
-  float* z3 = take((long long)G * 128);
-  float* a3 = take((long long)G * 128);
-  float* dz3 = take((long long)G * 128);
-  float* da2 = take((long long)G * 9216);
-  float* dz2 = take((long long)G * 36864);
-  float* dz1 = take((long long)G * 21632);
-  float* w2t = take((long long)K * 18432);
-  float* w2rot = take((long long)K * 18432);
-  float* slab = take((long long)G * 18432);
-  float* dlg = take((long long)G * C);  // last: keeps the rest 16 B aligned
-  TORCH_CHECK(f - work_f.data_ptr<float>() <= work_f.numel(),
-              "mega float workspace too small");
-  TORCH_CHECK(work_i.numel() >= G, "mega int workspace too small");
-  unsigned char* u = work_b.data_ptr<unsigned char>();
-  unsigned char* pidx = u;
-  unsigned char* m2 = u + (long long)G * 9216;
-  unsigned char* m3 = u + (long long)G * 9216 * 2;
-  TORCH_CHECK(work_b.numel() >= (long long)G * (9216 * 2 + 128),
-              "mega byte workspace too small");
+  TORCH_CHECK(row_bases_dev.scalar_type() == torch::kInt64 &&
+              order_offs_dev.scalar_type() == torch::kInt64 &&
+              counts_host.is_contiguous() && counts_host.dim() == 1);
+  // the mega driver rejects empty clients
+  check_client_meta(shard_x, shard_y, orders_dev, row_bases_dev.cpu(),
+                    order_offs_dev.cpu(), counts_host, /*allow_empty=*/false);
+  CnnWorkspace ws = slice_ws(work_f, work_i, work_b, (long long)K * bs, K, C);
   TORCH_CHECK(work_d.numel() >= (mu > 0.0 ? 3 : 2) * K,
               "mega double workspace too small");
   launch_cnn_round_mega(
@@ -857,9 +852,7 @@ void cnn_round_mega(torch::Tensor shard_x, torch::Tensor shard_y,
       reinterpret_cast<const long long*>(seeds_dev.data_ptr<int64_t>()),
       K, (int)bs, (int)C, server_params.data_ptr<float>(),
       params_stack.data_ptr<float>(), grads_stack.data_ptr<float>(),
-      round_accum.data_ptr<float>(),
-      xb, a1, r2, a2, z3, a3, dlg, dz3, da2, dz2, dz1, w2t, w2rot, slab,
-      work_i.data_ptr<int>(), pidx, m2, m3, work_d.data_ptr<double>(),
+      round_accum.data_ptr<float>(), ws, work_d.data_ptr<double>(),
       lr_t.data_ptr<float>(), (float)max_norm, (float)p1, (float)p2,
       stats_out.data_ptr<float>(), loss_out.data_ptr<float>(),
       cur_stream(), use_bf16 ? 1 : 0, (float)mu,
@@ -1017,6 +1010,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("segmented_sqnorm", &segmented_sqnorm);
   m.def("quant_bin_mask", &quant_bin_mask);
   m.def("gru_gates", &gru_gates);
+  m.def("cnn_workspace_sizes", &cnn_workspace_sizes_py,
+        "(n_float, n_int, n_byte) of the CNN workspace of G rows over K "
+        "clients with C classes");
   m.def("cnn_epoch", &cnn_epoch,
         py::arg("shard_x"), py::arg("shard_y"), py::arg("order"), py::arg("bs"), py::arg("C"), py::arg("params"), py::arg("grads"), py::arg("work_f"), py::arg("work_i"), py::arg("work_b"), py::arg("work_d"), py::arg("lr_t"), py::arg("max_norm"), py::arg("p1"), py::arg("p2"), py::arg("stats_acc"), py::arg("loss_acc"), py::arg("seed"), py::arg("use_bf16"),
         py::arg("server") = py::none(), py::arg("mu") = 0.0);

@@ -18,12 +18,13 @@
 // where a per-client grid (120 blocks) underfills the 256-CU chip.  The
 // per-client epoch (launch_cnn_epoch) launches the same kernels at K = 1
 // with bs := the batch's actual row count and the client's own arena as
-// the stack.  Only the ops that read per-client metadata (gather, the
-// conv2 forward's pool/dropout epilogue, the bf16 path's pool dropout,
-// fc1 reduce, loss) have two thin __global__ wrappers
-// around one __device__ body: the mega wrapper reads seeds[k]/counts[k]
-// from device arrays, the per-client one takes them as launch arguments
-// so that path uploads nothing.
+// the stack.  Both drivers issue a batch-step through ONE host function,
+// cnn_step.  The ops that read per-client metadata (gather, the conv2
+// forward's pool/dropout epilogue, the bf16 path's pool dropout, fc1
+// reduce, loss) are templates over a by-value step-metadata argument:
+// StepMetaDev (mega round) points at the seeds[k]/counts[k] device arrays,
+// StepMetaOne (K = 1) carries the same facts as launch scalars, so that
+// path uploads nothing.
 //
 // Ragged handling is free of masks in the backward chain: the gather
 // zero-fills inactive rows (b >= B_k(t)) and writes yb = -1, the loss
@@ -58,6 +59,49 @@ __device__ __forceinline__ int mega_Bk(const long long* counts, int k,
   long long rem = counts[k] - (long long)t * bs;
   return rem <= 0 ? 0 : (rem < bs ? (int)rem : bs);
 }
+
+// Who is in this batch-step, passed by value to the kernels that read
+// per-client metadata (they are templates over the form).  Two forms with
+// the same accessors: the mega round's points at the [K] device arrays and
+// carries the step index t; the per-client epoch's (K = 1) carries the same
+// facts as launch scalars, so that path uploads nothing.  The form is a
+// type, so no accessor costs a select at run time.
+struct StepMetaDev {
+  const long long* row_bases;
+  const long long* order_offs;
+  const long long* counts;
+  const long long* seeds;
+  int t;
+  static constexpr bool DEV = true;
+  static constexpr unsigned long long seed = 0;  // unused in this form
+  // rows of client k at this step
+  __device__ __forceinline__ int rows(int k, int bs) const {
+    return mega_Bk(counts, k, t, bs);
+  }
+  __device__ __forceinline__ unsigned long long seed_of(int k) const {
+    return (unsigned long long)seeds[k];
+  }
+  // shard row that batch row b of client k gathers
+  __device__ __forceinline__ long long src_row(
+      const long long* __restrict__ orders, int k, int b, int bs) const {
+    return row_bases[k] + orders[order_offs[k] + (long long)t * bs + b];
+  }
+};
+struct StepMetaOne {
+  long long row_base, start;  // shard row offset; batch start in `orders`
+  int B;                      // rows of this batch
+  unsigned long long seed;
+  static constexpr bool DEV = false;
+  static constexpr const long long* seeds = nullptr;  // unused in this form
+  __device__ __forceinline__ int rows(int, int) const { return B; }
+  __device__ __forceinline__ unsigned long long seed_of(int) const {
+    return seed;
+  }
+  __device__ __forceinline__ long long src_row(
+      const long long* __restrict__ orders, int, int b, int) const {
+    return row_base + orders[start + b];
+  }
+};
 
 __global__ void k_copy_stack(float* __restrict__ dst,
                              const float* __restrict__ src, long long P,
@@ -97,52 +141,27 @@ __global__ void k_cnn_axpy(float* __restrict__ y, const float* __restrict__ x,
 // gather a shuffled batch from the device-resident shard: element j of
 // batch row g comes from shard row src
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ void gather_elem(
-    const float* __restrict__ shard_x, const long long* __restrict__ shard_y,
-    long long src, int j, long long i, long long g,
-    float* __restrict__ xb, int* __restrict__ yb) {
-  xb[i] = shard_x[src * 784 + j];
-  if (j == 0) yb[g] = (int)shard_y[src];
-}
-
-__global__ void k_gather_batch(const float* __restrict__ shard_x,
-                               const long long* __restrict__ shard_y,
-                               const long long* __restrict__ order,
-                               long long start, long long row_base, int B,
-                               float* __restrict__ xb,
-                               int* __restrict__ yb) {
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < B * 784;
-       i += gridDim.x * blockDim.x) {
-    int b = i / 784, j = i % 784;
-    gather_elem(shard_x, shard_y, row_base + order[start + b], j, i, b,
-                xb, yb);
-  }
-}
-
+template <typename Meta>
 __global__ void k_gather_mb(const float* __restrict__ shard_x,
                             const long long* __restrict__ shard_y,
                             const long long* __restrict__ orders,
-                            const long long* __restrict__ row_bases,
-                            const long long* __restrict__ order_offs,
-                            const long long* __restrict__ counts,
-                            int t, int bs, int K,
+                            Meta meta, int bs, int K,
                             float* __restrict__ xb, int* __restrict__ yb,
                             double* __restrict__ acc2k, int n_acc) {
   int G = K * bs;
-  // first kernel of a batch-step: zero the clip's per-client sum / sumsq
-  // slots (2K; 3K under FedProx) — their last reader, the previous step's
-  // k_clip_sgd_mb, precedes this kernel in stream order
+  // first kernel of a batch-step: zero the clip's sum / sumsq slots (2 per
+  // client; 3 under FedProx) — their last reader, the previous step's clip
+  // kernel, precedes this kernel in stream order
   if (blockIdx.x == 0)
     for (int q = threadIdx.x; q < n_acc; q += blockDim.x) acc2k[q] = 0.0;
   for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
        i < (long long)G * 784; i += (long long)gridDim.x * blockDim.x) {
     int g = (int)(i / 784), j = (int)(i % 784);
     int k = g / bs, b = g % bs;
-    int Bk = mega_Bk(counts, k, t, bs);
-    if (b < Bk) {
-      long long src = row_bases[k]
-          + orders[order_offs[k] + (long long)t * bs + b];
-      gather_elem(shard_x, shard_y, src, j, i, g, xb, yb);
+    if (b < meta.rows(k, bs)) {
+      long long src = meta.src_row(orders, k, b, bs);
+      xb[i] = shard_x[src * 784 + j];
+      if (j == 0) yb[g] = (int)shard_y[src];
     } else {
       xb[i] = 0.f;
       if (j == 0) yb[g] = -1;
@@ -373,37 +392,21 @@ void k_conv2_fwd_mfma_mb(const float* __restrict__ a1,
                         0ull, nullptr, nullptr, nullptr);
 }
 
-// the two metadata wrappers of the POOL form: seeds[k] from the device
-// array (mega round) or the seed as a launch argument (K = 1)
+// the POOL form: client k draws from meta's seed
+template <typename Meta>
 __global__ __launch_bounds__(256)
 __attribute__((amdgpu_waves_per_eu(5, 5)))
 void k_conv2_fwd_pool_mfma_mb(const float* __restrict__ a1,
                               const float* __restrict__ w2t_stack,
                               const float* __restrict__ params, long long P,
                               long long ob2, int bs, int K, float p1,
-                              const long long* __restrict__ seeds,
-                              unsigned long long offset,
+                              Meta meta, unsigned long long offset,
                               float* __restrict__ a2,
                               unsigned char* __restrict__ pidx,
                               unsigned char* __restrict__ m2) {
   int k = (int)(blockIdx.x / C2F_SLABS / bs);
   conv2_fwd_body<true>(a1, w2t_stack, params, P, ob2, bs, nullptr, p1,
-                       (unsigned long long)seeds[k], offset, a2, pidx, m2);
-}
-
-__global__ __launch_bounds__(256)
-__attribute__((amdgpu_waves_per_eu(5, 5)))
-void k_conv2_fwd_pool_mfma(const float* __restrict__ a1,
-                           const float* __restrict__ w2t_stack,
-                           const float* __restrict__ params, long long P,
-                           long long ob2, int bs, int K, float p1,
-                           unsigned long long seed,
-                           unsigned long long offset,
-                           float* __restrict__ a2,
-                           unsigned char* __restrict__ pidx,
-                           unsigned char* __restrict__ m2) {
-  conv2_fwd_body<true>(a1, w2t_stack, params, P, ob2, bs, nullptr, p1, seed,
-                       offset, a2, pidx, m2);
+                       meta.seed_of(k), offset, a2, pidx, m2);
 }
 
 // maxpool 2x2 + dropout(p1) of pool cell i, whose 2x2 window starts at
@@ -411,11 +414,9 @@ void k_conv2_fwd_pool_mfma(const float* __restrict__ a1,
 // ReLU gate max > 0 (bit 2: all the backward needs of r2) + mask.  The Philox
 // key is (seed, li >> 2, batch offset) with li the CLIENT-LOCAL cell
 // index, so a client's masks do not depend on which driver or which
-// stack slot trains it.  Index is the wrapper's own index width (int
-// per client, long long for the stack).
-template <typename Index>
+// stack slot trains it.
 __device__ __forceinline__ void pool_drop_cell(
-    const float* __restrict__ base, Index i, Index li, float p1,
+    const float* __restrict__ base, long long i, long long li, float p1,
     float inv_keep, unsigned long long seed, unsigned long long offset,
     float* __restrict__ a2, unsigned char* __restrict__ pidx,
     unsigned char* __restrict__ m2) {
@@ -439,26 +440,9 @@ __device__ __forceinline__ void pool_drop_cell(
   a2[i] = keep ? m * inv_keep : 0.f;
 }
 
-__global__ void k_pool_drop_fwd(const float* __restrict__ r2, int B,
-                                float p1, unsigned long long seed,
-                                unsigned long long offset,
-                                float* __restrict__ a2,
-                                unsigned char* __restrict__ pidx,
-                                unsigned char* __restrict__ m2) {
-  int total = B * 64 * 144;
-  float inv_keep = (p1 < 1.f) ? 1.f / (1.f - p1) : 0.f;
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total;
-       i += gridDim.x * blockDim.x) {
-    int px = i % 12, py = (i / 12) % 12, c = (i / 144) % 64, b = i / 9216;
-    const float* base =
-        r2 + (((long long)b * 64 + c) * 24 + 2 * py) * 24 + 2 * px;
-    pool_drop_cell(base, i, i, p1, inv_keep, seed, offset, a2, pidx, m2);
-  }
-}
-
+template <typename Meta>
 __global__ void k_pool_drop_fwd_mb(const float* __restrict__ r2, int bs,
-                                   int K, float p1,
-                                   const long long* __restrict__ seeds,
+                                   int K, float p1, Meta meta,
                                    unsigned long long offset,
                                    float* __restrict__ a2,
                                    unsigned char* __restrict__ pidx,
@@ -473,8 +457,8 @@ __global__ void k_pool_drop_fwd_mb(const float* __restrict__ r2, int bs,
     int k = (int)(g / bs), b = (int)(g % bs);
     const float* base = r2 + ((g * 64 + c) * 24 + 2 * py) * 24 + 2 * px;
     long long li = (long long)b * 9216 + (i % 9216);
-    pool_drop_cell(base, i, li, p1, inv_keep, (unsigned long long)seeds[k],
-                   offset, a2, pidx, m2);
+    pool_drop_cell(base, i, li, p1, inv_keep, meta.seed_of(k), offset, a2,
+                   pidx, m2);
   }
 }
 
@@ -672,26 +656,18 @@ __device__ __forceinline__ void fc1_reduce_elem(
   a3[i] = keep ? r / (1.f - p2) : 0.f;
 }
 
-template <int SPLIT>
-__device__ __forceinline__ void fc1_reduce_client(
-    const float* __restrict__ slab, const float* __restrict__ b3, int B,
-    float p2, unsigned long long seed, unsigned long long offset,
-    float* __restrict__ z3, float* __restrict__ a3,
-    unsigned char* __restrict__ m3) {
-  int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= B * 128) return;
-  int b = i / 128, j = i % 128;
-  fc1_reduce_elem<SPLIT>(slab, b3[j], B, b, j, i, i, p2, seed, offset,
-                         z3, a3, m3);
-}
-
-template <int SPLIT>
+// DEV = StepMetaDev's form: seeds[k]; else the one `seed`.  The two fold
+// kernels take the pair as plain arguments, not as a metadata struct: the
+// fold's register budget is tight, and with the seeds pointer inside a
+// by-value struct (no longer a restrict kernel argument) the fp32 fold went
+// from 96 to 97 VGPRs and lost a wave, the bf16 fold from 58 to 105.
+template <int SPLIT, bool DEV>
 __device__ __forceinline__ void fc1_reduce_stack(
     const float* __restrict__ slab, const float* __restrict__ params,
     long long P, long long ob3, int bs, int K, float p2,
-    const long long* __restrict__ seeds, unsigned long long offset,
-    float* __restrict__ z3, float* __restrict__ a3,
-    unsigned char* __restrict__ m3) {
+    const long long* __restrict__ seeds, unsigned long long seed,
+    unsigned long long offset, float* __restrict__ z3,
+    float* __restrict__ a3, unsigned char* __restrict__ m3) {
   long long total = (long long)K * bs * 128;
   for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
        i < total; i += (long long)gridDim.x * blockDim.x) {
@@ -701,32 +677,22 @@ __device__ __forceinline__ void fc1_reduce_stack(
     fc1_reduce_elem<SPLIT>(slab + (long long)k * SPLIT * bs * 128,
                            params[(long long)k * P + ob3 + j], bs, b, j, i,
                            (long long)b * 128 + j, p2,
-                           (unsigned long long)seeds[k], offset,
+                           DEV ? (unsigned long long)seeds[k] : seed, offset,
                            z3, a3, m3);
   }
 }
 
-__global__ __launch_bounds__(FC1R_BLK) void k_fc1_fwd_reduce(const float* __restrict__ slab,
-                                 const float* __restrict__ b3, int B,
-                                 float p2, unsigned long long seed,
-                                 unsigned long long offset,
-                                 float* __restrict__ z3,
-                                 float* __restrict__ a3,
-                                 unsigned char* __restrict__ m3) {
-  fc1_reduce_client<FC1_SPLIT>(slab, b3, B, p2, seed, offset, z3, a3, m3);
-}
-
-__global__ __launch_bounds__(FC1R_BLK) void k_fc1_fwd_reduce_mb(const float* __restrict__ slab,
-                                    const float* __restrict__ params,
-                                    long long P, long long ob3, int bs,
-                                    int K, float p2,
-                                    const long long* __restrict__ seeds,
-                                    unsigned long long offset,
-                                    float* __restrict__ z3,
-                                    float* __restrict__ a3,
-                                    unsigned char* __restrict__ m3) {
-  fc1_reduce_stack<FC1_SPLIT>(slab, params, P, ob3, bs, K, p2, seeds, offset,
-                              z3, a3, m3);
+template <bool DEV>
+__global__ __launch_bounds__(FC1R_BLK)
+void k_fc1_fwd_reduce_mb(const float* __restrict__ slab,
+                         const float* __restrict__ params, long long P,
+                         long long ob3, int bs, int K, float p2,
+                         const long long* __restrict__ seeds,
+                         unsigned long long seed, unsigned long long offset,
+                         float* __restrict__ z3, float* __restrict__ a3,
+                         unsigned char* __restrict__ m3) {
+  fc1_reduce_stack<FC1_SPLIT, DEV>(slab, params, P, ob3, bs, K, p2, seeds,
+                                   seed, offset, z3, a3, m3);
 }
 
 // fc2 + softmax + CE for one sample row (one block): logits = W4 @ a3 +
@@ -779,30 +745,13 @@ __device__ __forceinline__ void fc2_loss_row(
   }
 }
 
-__global__ void k_fc2_loss_fwd(const float* __restrict__ a3,
-                               const float* __restrict__ w4,
-                               const float* __restrict__ b4,
-                               const int* __restrict__ yb, int B, int C,
-                               float* __restrict__ dlogits,
-                               float* __restrict__ loss_acc,
-                               const float* __restrict__ z3,
-                               const unsigned char* __restrict__ m3,
-                               float p2, float* __restrict__ dz3) {
-  extern __shared__ float sm[];
-  int b = blockIdx.x;
-  fc2_loss_row(a3 + (long long)b * 128, w4, b4, yb[b], B, C,
-               dlogits + (long long)b * C, loss_acc, sm,
-               z3 + (long long)b * 128, m3 + (long long)b * 128, p2,
-               dz3 + (long long)b * 128);
-}
-
 // one block per super-row g; yb<0 (inactive) rows zero their dlogits and
 // their dz3 (what backward-data gives from zero dlogits)
+template <typename Meta>
 __global__ void k_fc2_loss_fwd_mb(const float* __restrict__ a3,
                                   const float* __restrict__ params,
                                   long long P, long long ow4, long long ob4,
-                                  const long long* __restrict__ counts,
-                                  int t, int bs, int K, int C,
+                                  Meta meta, int bs, int K, int C,
                                   const int* __restrict__ yb,
                                   float* __restrict__ dlogits,
                                   float* __restrict__ loss_out,
@@ -821,7 +770,7 @@ __global__ void k_fc2_loss_fwd_mb(const float* __restrict__ a3,
   }
   fc2_loss_row(a3 + g * 128, params + (long long)k * P + ow4,
                params + (long long)k * P + ob4, target,
-               mega_Bk(counts, k, t, bs), C, dlogits + g * C, loss_out + k,
+               meta.rows(k, bs), C, dlogits + g * C, loss_out + k,
                sm, z3 + g * 128, m3 + g * 128, p2, dz3 + g * 128);
 }
 
@@ -1975,27 +1924,18 @@ void k_fc1_fwd_mfma_mb_bf16(const float* __restrict__ a2,
     }
 }
 
-__global__ __launch_bounds__(FC1R_BLK) void k_fc1_fwd_reduce_bf16(const float* __restrict__ slab,
-                                      const float* __restrict__ b3, int B,
-                                      float p2, unsigned long long seed,
-                                      unsigned long long offset,
-                                      float* __restrict__ z3,
-                                      float* __restrict__ a3,
-                                      unsigned char* __restrict__ m3) {
-  fc1_reduce_client<FC1B_SPLIT>(slab, b3, B, p2, seed, offset, z3, a3, m3);
-}
-
-__global__ __launch_bounds__(FC1R_BLK) void k_fc1_fwd_reduce_mb_bf16(const float* __restrict__ slab,
-                                         const float* __restrict__ params,
-                                         long long P, long long ob3, int bs,
-                                         int K, float p2,
-                                         const long long* __restrict__ seeds,
-                                         unsigned long long offset,
-                                         float* __restrict__ z3,
-                                         float* __restrict__ a3,
-                                         unsigned char* __restrict__ m3) {
-  fc1_reduce_stack<FC1B_SPLIT>(slab, params, P, ob3, bs, K, p2, seeds,
-                               offset, z3, a3, m3);
+template <bool DEV>
+__global__ __launch_bounds__(FC1R_BLK)
+void k_fc1_fwd_reduce_mb_bf16(const float* __restrict__ slab,
+                              const float* __restrict__ params, long long P,
+                              long long ob3, int bs, int K, float p2,
+                              const long long* __restrict__ seeds,
+                              unsigned long long seed,
+                              unsigned long long offset,
+                              float* __restrict__ z3, float* __restrict__ a3,
+                              unsigned char* __restrict__ m3) {
+  fc1_reduce_stack<FC1B_SPLIT, DEV>(slab, params, P, ob3, bs, K, p2, seeds,
+                                    seed, offset, z3, a3, m3);
 }
 
 // bf16 MFMA probe: one v_mfma_f32_16x16x32_bf16 with the documented
@@ -2022,28 +1962,125 @@ __global__ void k_mfma_bf16_probe(const __bf16* __restrict__ A,   // [16][32]
 
 
 // ---------------------------------------------------------------------------
-// per-client epoch driver: loops every batch of ONE client's local epoch,
-// launching the stacked kernels at K = 1 (bs := this batch's row count,
-// the client's arena as the stack) + clip-stats + SGD via flat_ops.hip.
+// ONE batch-step, shared by both drivers: the launches from the gather
+// through conv1's backward, for K clients of bs rows each (G = K*bs).  The
+// per-client epoch calls it with K = 1, bs := this batch's row count and
+// its arena as the stack; the mega round with (K, bs, t).  `meta` says who
+// is in the step (StepMetaDev / StepMetaOne), t keys the dropout streams,
+// and the gather zeroes the n_acc doubles at `acc` for the caller's clip
+// tail.
 // ---------------------------------------------------------------------------
 
 // CNN_EPOCH_DEBUG=1: synchronize + check after every launch so a device
 // fault names the kernel that raised it (diagnostics only — the hot path
 // never syncs)
-#define EPOCH_CHK(name)                                                    \
+static bool epoch_dbg() {
+  static const bool on = getenv("CNN_EPOCH_DEBUG") != nullptr;
+  return on;
+}
+#define EPOCH_CHK(name, t, bs)                                             \
   do {                                                                     \
-    if (epoch_dbg) {                                                       \
+    if (epoch_dbg()) {                                                     \
       hipError_t e_ = hipStreamSynchronize(s);                             \
       hipError_t e2_ = hipGetLastError();                                  \
       if (e_ != hipSuccess || e2_ != hipSuccess) {                         \
-        fprintf(stderr, "cnn_epoch fault after %s (it=%d B=%d): %s / %s\n",\
-                name, it, B, hipGetErrorString(e_), hipGetErrorString(e2_));\
+        fprintf(stderr, "cnn_step fault after %s (t=%d bs=%d): %s / %s\n", \
+                name, t, bs, hipGetErrorString(e_),                        \
+                hipGetErrorString(e2_));                                   \
         fflush(stderr);                                                    \
         abort();                                                           \
       }                                                                    \
     }                                                                      \
   } while (0)
 
+template <typename Meta>
+static void cnn_step(const float* shard_x, const long long* shard_y,
+                     const long long* orders, const Meta& meta, int t,
+                     int K, int bs, int C, float* params, float* grads,
+                     const CnnWorkspace& ws, double* acc, int n_acc,
+                     float p1, float p2, float* loss_out, int use_bf16,
+                     hipStream_t s) {
+  CnnOffsets o = cnn_offsets(C);
+  long long P = o.total;
+  int G = K * bs;
+  // grid of `blk`-thread blocks covering per_row elements of each of G rows
+  auto blocks = [G](long long per_row, int blk) {
+    return dim3((int)((G * per_row + blk - 1) / blk));
+  };
+  static_assert(18432 % FBLK == 0, "w2_grid: whole blocks per client");
+  dim3 w2_grid(K * (18432 / FBLK));  // one thread per W2 element
+  unsigned long long off = (unsigned long long)t;  // Philox batch offset
+#define STEP(kernel, grid, block, shmem, ...)                              \
+  hipLaunchKernelGGL(kernel, grid, block, shmem, s, __VA_ARGS__);          \
+  EPOCH_CHK(#kernel, t, bs)
+  STEP(k_gather_mb<Meta>, blocks(784, FBLK), dim3(FBLK), 0, shard_x, shard_y,
+       orders, meta, bs, K, ws.xb, ws.yb, acc, n_acc);
+  STEP(k_conv1_fwd_mb, blocks(21632, FBLK), dim3(FBLK), 0, ws.xb, params,
+       P, o.w1, o.b1, bs, K, ws.a1);
+  if (use_bf16) {
+    // bf16 kernels read w2 directly (LDS staging converts); bwd-data
+    // wants its own [ci][k'] bf16 layout, which fits in ws.w2rot
+    STEP(k_w2rotbf_mb, w2_grid, dim3(FBLK), 0, params, P, o.w2, K,
+         reinterpret_cast<__bf16*>(ws.w2rot));
+    STEP(k_conv2_fwd_mfma_mb_bf16, dim3(G * 9), dim3(FBLK), 0, ws.a1, params,
+         P, o.w2, o.b2, bs, K, ws.r2);
+    STEP(k_pool_drop_fwd_mb<Meta>, blocks(9216, FBLK), dim3(FBLK), 0, ws.r2,
+         bs, K, p1, meta, off, ws.a2, ws.pidx, ws.m2);
+    STEP(k_fc1_fwd_mfma_mb_bf16, dim3(K * FC1B_SPLIT), dim3(FBLK), 0, ws.a2,
+         params, P, o.w3, bs, K, ws.wsl);
+    STEP(k_fc1_fwd_reduce_mb_bf16<Meta::DEV>, blocks(128, FC1R_BLK),
+         dim3(FC1R_BLK), 0, ws.wsl, params, P, o.b3, bs, K, p2, meta.seeds,
+         meta.seed, off, ws.z3, ws.a3, ws.m3);
+  } else {
+    STEP(k_w2_layouts_mb, w2_grid, dim3(FBLK), 0, params, P, o.w2, K, ws.w2t,
+         ws.w2rot);
+    // conv2 + pool + dropout in one kernel: no r2 on the fp32 path
+    STEP(k_conv2_fwd_pool_mfma_mb<Meta>, dim3(G * C2F_SLABS), dim3(FBLK), 0,
+         ws.a1, ws.w2t, params, P, o.b2, bs, K, p1, meta, off, ws.a2,
+         ws.pidx, ws.m2);
+    STEP(k_fc1_fwd_mfma_mb, dim3(K * FC1_SPLIT), dim3(FBLK), 0, ws.a2,
+         params, P, o.w3, bs, K, ws.wsl);
+    STEP(k_fc1_fwd_reduce_mb<Meta::DEV>, blocks(128, FC1R_BLK),
+         dim3(FC1R_BLK), 0, ws.wsl, params, P, o.b3, bs, K, p2, meta.seeds,
+         meta.seed, off, ws.z3, ws.a3, ws.m3);
+  }
+  STEP(k_fc2_loss_fwd_mb<Meta>, dim3(G), dim3(FBLK), C * (int)sizeof(float),
+       ws.a3, params, P, o.w4, o.b4, meta, bs, K, C, ws.yb, ws.dlogits,
+       loss_out, ws.z3, ws.m3, p2, ws.dz3);
+  STEP(k_fc2_bwd_w_mb, dim3(K * ((C * 128 + FBLK - 1) / FBLK)), dim3(FBLK), 0,
+       ws.dlogits, ws.a3, grads, P, o.w4, o.b4, bs, K, C);
+  STEP(k_fc1_bwd_w_mfma_mb, dim3(K * 144), dim3(FBLK), 0, ws.dz3, ws.a2,
+       grads, P, o.w3, grads, P, o.b3, bs, K);
+  STEP(k_fc1_bwd_x_mfma_mb, dim3(K * FC1X_BLKS), dim3(64 * FC1X_WAVES), 0,
+       ws.dz3, params, P, o.w3, bs, K, ws.da2);
+  STEP(k_pool_drop_bwd_bias_mb, dim3(K * 64), dim3(FBLK), 0, ws.da2, ws.pidx,
+       ws.m2, bs, K, p1, ws.dz2, grads, P, o.b2);
+  if (use_bf16) {
+    STEP(k_conv2_bwd_w_mfma_mb_bf16, dim3(18 * G), dim3(FBLK), 0, ws.dz2,
+         ws.a1, bs, K, ws.wsl);
+  } else {
+    STEP(k_conv2_bwd_w_mfma_mb, dim3(9 * G), dim3(128), 0, ws.dz2, ws.a1, bs,
+         K, ws.wsl);
+  }
+  STEP(k_conv2_bwd_w_fold_mb, w2_grid, dim3(FBLK), 0, ws.wsl, grads, P, o.w2,
+       bs, K);
+  if (use_bf16) {
+    STEP(k_conv2_bwd_x_mfma_mb_bf16, dim3(G * 22), dim3(FBLK), 0, ws.dz2,
+         reinterpret_cast<const __bf16*>(ws.w2rot), bs, K, ws.a1, ws.dz1);
+  } else {
+    STEP(k_conv2_bwd_x_mfma_mb, dim3(G * C2X_BLKS), dim3(FBLK), 0, ws.dz2,
+         ws.w2rot, ws.a1, bs, K, ws.dz1);
+  }
+  STEP(k_conv1_bwd_w_mb, dim3(K * 32), dim3(1024), 0, ws.xb, ws.dz1, grads,
+       P, o.w1, o.b1, bs, K);
+#undef STEP
+}
+
+// ---------------------------------------------------------------------------
+// per-client epoch driver: loops every batch of ONE client's local epoch:
+// cnn_step at K = 1 (bs := this batch's row count, the client's arena as
+// the stack) + clip-stats + SGD via flat_ops.hip.
+// ---------------------------------------------------------------------------
 extern "C" void launch_cnn_epoch(
     const float* shard_x, const long long* shard_y, const long long* order,
     long long n, int bs, int C, float* params, float* grads,
@@ -2051,139 +2088,45 @@ extern "C" void launch_cnn_epoch(
     float* stats_acc, float* loss_acc, unsigned long long seed,
     hipStream_t s, long long row_base, int use_bf16,
     const float* server_params, float mu) {
-  static const bool epoch_dbg = getenv("CNN_EPOCH_DEBUG") != nullptr;
-  CnnOffsets o = cnn_offsets(C);
-  long long P = o.total;
+  long long P = cnn_offsets(C).total;
   const int K = 1;
+  const bool prox = mu > 0.f;
   int n_batches = (int)((n + bs - 1) / bs);
   for (int it = 0; it < n_batches; ++it) {
     long long start = (long long)it * bs;
     int B = (int)((start + bs <= n) ? bs : (n - start));
-    unsigned long long off = (unsigned long long)it;
-    hipLaunchKernelGGL(k_gather_batch, dim3((B * 784 + FBLK - 1) / FBLK),
-                       dim3(FBLK), 0, s, shard_x, shard_y, order, start,
-                       row_base, B, ws.xb, ws.yb);
-    EPOCH_CHK("k_gather_batch");
-    hipLaunchKernelGGL(k_conv1_fwd_mb, dim3((B * 21632 + FBLK - 1) / FBLK),
-                       dim3(FBLK), 0, s, ws.xb, params, P, o.w1, o.b1, B, K,
-                       ws.a1);
-    EPOCH_CHK("k_conv1_fwd_mb");
-    if (use_bf16) {
-      // bf16 kernels read w2 directly (LDS staging converts); bwd-data
-      // wants its own [ci][k'] bf16 layout, which fits in ws.w2rot
-      hipLaunchKernelGGL(k_w2rotbf_mb, dim3((18432 + FBLK - 1) / FBLK),
-                         dim3(FBLK), 0, s, params, P, o.w2, K,
-                         reinterpret_cast<__bf16*>(ws.w2rot));
-      EPOCH_CHK("k_w2rotbf_mb");
-      hipLaunchKernelGGL(k_conv2_fwd_mfma_mb_bf16, dim3(B * 9), dim3(FBLK),
-                         0, s, ws.a1, params, P, o.w2, o.b2, B, K, ws.r2);
-      EPOCH_CHK("k_conv2_fwd_mfma_mb_bf16");
-      hipLaunchKernelGGL(k_pool_drop_fwd, dim3((B * 9216 + FBLK - 1) / FBLK),
-                         dim3(FBLK), 0, s, ws.r2, B, p1, seed, off, ws.a2,
-                         ws.pidx, ws.m2);
-      EPOCH_CHK("k_pool_drop_fwd");
-    } else {
-      hipLaunchKernelGGL(k_w2_layouts_mb, dim3((18432 + FBLK - 1) / FBLK),
-                         dim3(FBLK), 0, s, params, P, o.w2, K, ws.w2t,
-                         ws.w2rot);
-      EPOCH_CHK("k_w2_layouts_mb");
-      // conv2 + pool + dropout in one kernel: no r2 on the fp32 path
-      hipLaunchKernelGGL(k_conv2_fwd_pool_mfma, dim3(B * C2F_SLABS),
-                         dim3(FBLK), 0, s, ws.a1, ws.w2t, params, P, o.b2, B,
-                         K, p1, seed, off, ws.a2, ws.pidx, ws.m2);
-      EPOCH_CHK("k_conv2_fwd_pool_mfma");
-    }
-    if (use_bf16) {
-      hipLaunchKernelGGL(k_fc1_fwd_mfma_mb_bf16, dim3(FC1B_SPLIT), dim3(FBLK),
-                         0, s, ws.a2, params, P, o.w3, B, K, ws.wsl);
-      EPOCH_CHK("k_fc1_fwd_mfma_mb_bf16");
-      hipLaunchKernelGGL(k_fc1_fwd_reduce_bf16,
-                         dim3((B * 128 + FC1R_BLK - 1) / FC1R_BLK),
-                         dim3(FC1R_BLK), 0, s, ws.wsl, params + o.b3, B, p2, seed,
-                         off, ws.z3, ws.a3, ws.m3);
-    } else {
-      hipLaunchKernelGGL(k_fc1_fwd_mfma_mb, dim3(FC1_SPLIT), dim3(FBLK), 0, s,
-                         ws.a2, params, P, o.w3, B, K, ws.wsl);
-      EPOCH_CHK("k_fc1_fwd_mfma_mb");
-      hipLaunchKernelGGL(k_fc1_fwd_reduce,
-                         dim3((B * 128 + FC1R_BLK - 1) / FC1R_BLK),
-                         dim3(FC1R_BLK), 0, s, ws.wsl, params + o.b3, B, p2, seed,
-                         off, ws.z3, ws.a3, ws.m3);
-    }
-    EPOCH_CHK("k_fc1_fwd_reduce");
-    hipLaunchKernelGGL(k_fc2_loss_fwd, dim3(B), dim3(FBLK),
-                       C * (int)sizeof(float), s, ws.a3, params + o.w4,
-                       params + o.b4, ws.yb, B, C, ws.dlogits, loss_acc,
-                       ws.z3, ws.m3, p2, ws.dz3);
-    EPOCH_CHK("k_fc2_loss_fwd");
-    hipLaunchKernelGGL(k_fc2_bwd_w_mb, dim3((C * 128 + FBLK - 1) / FBLK),
-                       dim3(FBLK), 0, s, ws.dlogits, ws.a3, grads, P, o.w4,
-                       o.b4, B, K, C);
-    EPOCH_CHK("k_fc2_bwd_w_mb");
-    hipLaunchKernelGGL(k_fc1_bwd_w_mfma_mb, dim3(144), dim3(FBLK), 0, s,
-                       ws.dz3, ws.a2, grads, P, o.w3, grads, P, o.b3, B, K);
-    EPOCH_CHK("k_fc1_bwd_w_mfma_mb");
-    hipLaunchKernelGGL(k_fc1_bwd_x_mfma_mb, dim3(FC1X_BLKS),
-                       dim3(64 * FC1X_WAVES), 0, s,
-                       ws.dz3, params, P, o.w3, B, K, ws.da2);
-    EPOCH_CHK("k_fc1_bwd_x_mfma_mb");
-    hipLaunchKernelGGL(k_pool_drop_bwd_bias_mb, dim3(64), dim3(FBLK), 0, s,
-                       ws.da2, ws.pidx, ws.m2, B, K, p1, ws.dz2, grads, P,
-                       o.b2);
-    EPOCH_CHK("k_pool_drop_bwd_bias_mb");
-    if (use_bf16) {
-      hipLaunchKernelGGL(k_conv2_bwd_w_mfma_mb_bf16, dim3(18 * B), dim3(FBLK),
-                         0, s, ws.dz2, ws.a1, B, K, ws.wsl);
-    } else {
-      hipLaunchKernelGGL(k_conv2_bwd_w_mfma_mb, dim3(9 * B), dim3(128), 0,
-                         s, ws.dz2, ws.a1, B, K, ws.wsl);
-    }
-    EPOCH_CHK("k_conv2_bwd_w_mfma_mb");
-    hipLaunchKernelGGL(k_conv2_bwd_w_fold_mb, dim3((18432 + FBLK - 1) / FBLK),
-                       dim3(FBLK), 0, s, ws.wsl, grads, P, o.w2, B, K);
-    EPOCH_CHK("k_conv2_bwd_w_fold_mb");
-    if (use_bf16)
-      hipLaunchKernelGGL(k_conv2_bwd_x_mfma_mb_bf16, dim3(B * 22), dim3(FBLK),
-                         0, s, ws.dz2,
-                         reinterpret_cast<const __bf16*>(ws.w2rot), B, K,
-                         ws.a1, ws.dz1);
-    else
-      hipLaunchKernelGGL(k_conv2_bwd_x_mfma_mb, dim3(B * C2X_BLKS),
-                         dim3(FBLK), 0, s, ws.dz2, ws.w2rot, ws.a1, B, K,
-                         ws.dz1);
-    EPOCH_CHK("k_conv2_bwd_x_mfma_mb");
-    hipLaunchKernelGGL(k_conv1_bwd_w_mb, dim3(32), dim3(1024), 0, s,
-                       ws.xb, ws.dz1, grads, P, o.w1, o.b1, B, K);
-    EPOCH_CHK("k_conv1_bwd_w_mb");
-    if (mu > 0.f) {
+    // the gather zeroes what this step's clip tail accumulates into
+    cnn_step(shard_x, shard_y, order, StepMetaOne{row_base, start, B, seed},
+             it, K, B, C, params, grads, ws,
+             prox ? ws.red_partials : ws.red_acc, prox ? 3 : 2, p1, p2,
+             loss_acc, use_bf16, s);
+    if (prox) {
       // FedProx: the PROX pair at K = 1, every step active; forms
       // g + mu (w - w_g) in registers and adds the regulariser to loss_acc
       ProxArgs px{params, K, server_params, mu, nullptr, 0, 0, nullptr,
                   loss_acc};
-      hipMemsetAsync(ws.red_partials, 0, 3 * sizeof(double), s);
       int blocks_per_k = (int)((P + SUMSQ_CHUNK - 1) / SUMSQ_CHUNK);
       hipLaunchKernelGGL(k_sumsq_mb<ProxArgs>, dim3(blocks_per_k),
                          dim3(FBLK), 0, s, grads, P, blocks_per_k,
                          ws.red_partials, px);
-      EPOCH_CHK("k_sumsq_mb<ProxArgs>");
+      EPOCH_CHK("k_sumsq_mb<ProxArgs>", it, B);
       int gkp = (int)((P + FBLK - 1) / FBLK); if (gkp > 4096) gkp = 4096;
       hipLaunchKernelGGL((k_clip_sgd_mb<false, ProxArgs>), dim3(gkp),
                          dim3(FBLK), 0, s, params, grads, P, K,
                          ws.red_partials, max_norm, 1e-6f, lr_t, stats_acc,
                          px);
-      EPOCH_CHK("k_clip_sgd_mb<ProxArgs>");
+      EPOCH_CHK("k_clip_sgd_mb<ProxArgs>", it, B);
       continue;
     }
     // fused clip + sufficient stats + SGD on the whole arena
-    hipMemsetAsync(ws.red_acc, 0, 2 * sizeof(double), s);
-    launch_sum_sumsq2(grads, o.total, ws.red_partials, ws.red_acc, s);
-    EPOCH_CHK("launch_sum_sumsq2");
-    launch_clip_apply_stats(grads, o.total, ws.red_acc, max_norm, 1e-6f,
+    launch_sum_sumsq2(grads, P, ws.red_partials, ws.red_acc, s);
+    EPOCH_CHK("launch_sum_sumsq2", it, B);
+    launch_clip_apply_stats(grads, P, ws.red_acc, max_norm, 1e-6f,
                             stats_acc, s);
-    EPOCH_CHK("launch_clip_apply_stats");
+    EPOCH_CHK("launch_clip_apply_stats", it, B);
     launch_sgd_step(params, grads, nullptr, 0.f, lr_t, 0.f, 0.f, 0.f, 0, 0,
-                    o.total, s);
-    EPOCH_CHK("launch_sgd_step");
+                    P, s);
+    EPOCH_CHK("launch_sgd_step", it, B);
   }
 }
 
@@ -2230,18 +2173,11 @@ extern "C" void launch_cnn_round_mega(
     const float* weights_dev, const long long* seeds_dev,
     int K, int bs, int C,
     const float* server_params, float* params_stack, float* grads_stack,
-    float* round_accum,
-    float* xb, float* a1, float* r2, float* a2, float* z3, float* a3,
-    float* dlogits, float* dz3, float* da2, float* dz2, float* dz1,
-    float* w2t_stack, float* w2rot_stack, float* slab,
-    int* yb, unsigned char* pidx, unsigned char* m2, unsigned char* m3,
-    double* acc2k,
+    float* round_accum, CnnWorkspace ws, double* acc2k,
     const float* lr_t, float max_norm, float p1, float p2,
     float* stats_out, float* loss_out, hipStream_t s, int use_bf16,
     float mu, const DgaArgs* dga, double* dga_out) {
-  CnnOffsets o = cnn_offsets(C);
-  long long P = o.total;
-  int G = K * bs;
+  long long P = cnn_offsets(C).total;
   const bool prox = mu > 0.f;  // FedProx: acc2k holds 3K doubles
   int max_batches = 0;
   for (int k = 0; k < K; ++k) {
@@ -2254,89 +2190,11 @@ extern "C" void launch_cnn_round_mega(
   hipLaunchKernelGGL(k_copy_stack, dim3(gkp), dim3(FBLK), 0, s,
                      params_stack, server_params, P, K);
   for (int t = 0; t < max_batches; ++t) {
-    unsigned long long off = (unsigned long long)t;
-    hipLaunchKernelGGL(k_gather_mb, dim3((G * 784 + FBLK - 1) / FBLK),
-                       dim3(FBLK), 0, s, shard_x, shard_y, orders_dev,
-                       row_bases_dev, order_offs_dev, counts_dev, t, bs, K,
-                       xb, yb, acc2k, prox ? 3 * K : 2 * K);
-    hipLaunchKernelGGL(k_conv1_fwd_mb,
-                       dim3((int)(((long long)G * 21632 + FBLK - 1) / FBLK)),
-                       dim3(FBLK), 0, s, xb, params_stack, P, o.w1, o.b1,
-                       bs, K, a1);
-    if (use_bf16) {
-      hipLaunchKernelGGL(k_w2rotbf_mb,
-                         dim3((int)(((long long)K * 18432 + FBLK - 1) / FBLK)),
-                         dim3(FBLK), 0, s, params_stack, P, o.w2, K,
-                         reinterpret_cast<__bf16*>(w2rot_stack));
-      hipLaunchKernelGGL(k_conv2_fwd_mfma_mb_bf16, dim3(G * 9), dim3(FBLK),
-                         0, s, a1, params_stack, P, o.w2, o.b2, bs, K, r2);
-      hipLaunchKernelGGL(k_pool_drop_fwd_mb,
-                         dim3((int)(((long long)G * 9216 + FBLK - 1) / FBLK)),
-                         dim3(FBLK), 0, s, r2, bs, K, p1, seeds_dev, off,
-                         a2, pidx, m2);
-    } else {
-      hipLaunchKernelGGL(k_w2_layouts_mb,
-                         dim3((int)(((long long)K * 18432 + FBLK - 1) / FBLK)),
-                         dim3(FBLK), 0, s, params_stack, P, o.w2, K,
-                         w2t_stack, w2rot_stack);
-      // conv2 + pool + dropout in one kernel: no r2 on the fp32 path
-      hipLaunchKernelGGL(k_conv2_fwd_pool_mfma_mb, dim3(G * C2F_SLABS),
-                         dim3(FBLK), 0, s, a1, w2t_stack, params_stack, P,
-                         o.b2, bs, K, p1, seeds_dev, off, a2, pidx, m2);
-    }
-    if (use_bf16) {
-      hipLaunchKernelGGL(k_fc1_fwd_mfma_mb_bf16, dim3(K * 36), dim3(FBLK),
-                         0, s, a2, params_stack, P, o.w3, bs, K, slab);
-      hipLaunchKernelGGL(k_fc1_fwd_reduce_mb_bf16,
-                         dim3((int)(((long long)G * 128 + FC1R_BLK - 1) /
-                                    FC1R_BLK)),
-                         dim3(FC1R_BLK), 0, s, slab, params_stack, P, o.b3, bs,
-                         K, p2, seeds_dev, off, z3, a3, m3);
-    } else {
-      hipLaunchKernelGGL(k_fc1_fwd_mfma_mb, dim3(K * FC1_SPLIT), dim3(FBLK),
-                         0, s, a2, params_stack, P, o.w3, bs, K, slab);
-      hipLaunchKernelGGL(k_fc1_fwd_reduce_mb,
-                         dim3((int)(((long long)G * 128 + FC1R_BLK - 1) /
-                                    FC1R_BLK)),
-                         dim3(FC1R_BLK), 0, s, slab, params_stack, P, o.b3, bs,
-                         K, p2, seeds_dev, off, z3, a3, m3);
-    }
-    hipLaunchKernelGGL(k_fc2_loss_fwd_mb, dim3(G), dim3(FBLK),
-                       C * (int)sizeof(float), s, a3, params_stack, P, o.w4,
-                       o.b4, counts_dev, t, bs, K, C, yb, dlogits, loss_out,
-                       z3, m3, p2, dz3);
-    int perk_fc2 = (C * 128 + FBLK - 1) / FBLK;
-    hipLaunchKernelGGL(k_fc2_bwd_w_mb, dim3(K * perk_fc2), dim3(FBLK), 0, s,
-                       dlogits, a3, grads_stack, P, o.w4, o.b4, bs, K, C);
-    hipLaunchKernelGGL(k_fc1_bwd_w_mfma_mb, dim3(K * 144), dim3(FBLK), 0, s,
-                       dz3, a2, grads_stack, P, o.w3, grads_stack, P, o.b3,
-                       bs, K);
-    hipLaunchKernelGGL(k_fc1_bwd_x_mfma_mb, dim3(K * FC1X_BLKS),
-                       dim3(64 * FC1X_WAVES), 0, s,
-                       dz3, params_stack, P, o.w3, bs, K, da2);
-    hipLaunchKernelGGL(k_pool_drop_bwd_bias_mb, dim3(K * 64), dim3(FBLK), 0,
-                       s, da2, pidx, m2, bs, K, p1, dz2, grads_stack, P,
-                       o.b2);
-    if (use_bf16) {
-      hipLaunchKernelGGL(k_conv2_bwd_w_mfma_mb_bf16, dim3(18 * G), dim3(FBLK),
-                         0, s, dz2, a1, bs, K, slab);
-    } else {
-      hipLaunchKernelGGL(k_conv2_bwd_w_mfma_mb, dim3(9 * G), dim3(128),
-                         0, s, dz2, a1, bs, K, slab);
-    }
-    int perk_fold = (18432 + FBLK - 1) / FBLK;
-    hipLaunchKernelGGL(k_conv2_bwd_w_fold_mb, dim3(K * perk_fold),
-                       dim3(FBLK), 0, s, slab, grads_stack, P, o.w2, bs, K);
-    if (use_bf16)
-      hipLaunchKernelGGL(k_conv2_bwd_x_mfma_mb_bf16, dim3(G * 22), dim3(FBLK),
-                         0, s, dz2,
-                         reinterpret_cast<const __bf16*>(w2rot_stack),
-                         bs, K, a1, dz1);
-    else
-      hipLaunchKernelGGL(k_conv2_bwd_x_mfma_mb, dim3(G * C2X_BLKS),
-                         dim3(FBLK), 0, s, dz2, w2rot_stack, a1, bs, K, dz1);
-    hipLaunchKernelGGL(k_conv1_bwd_w_mb, dim3(K * 32), dim3(1024), 0, s,
-                       xb, dz1, grads_stack, P, o.w1, o.b1, bs, K);
+    cnn_step(shard_x, shard_y, orders_dev,
+             StepMetaDev{row_bases_dev, order_offs_dev, counts_dev, seeds_dev,
+                         t},
+             t, K, bs, C, params_stack, grads_stack, ws, acc2k,
+             prox ? 3 * K : 2 * K, p1, p2, loss_out, use_bf16, s);
     // acc2k was zeroed by this step's k_gather_mb
     int blocks_per_k = (int)((P + SUMSQ_CHUNK - 1) / SUMSQ_CHUNK);
     if (prox) {
@@ -2461,9 +2319,11 @@ void launch_conv2_fwd_pool_mfma(const float* a1, const float* w2t,
                                 unsigned long long offset, float* a2,
                                 unsigned char* pidx, unsigned char* m2,
                                 hipStream_t s) {
-  hipLaunchKernelGGL(k_conv2_fwd_pool_mfma_mb, dim3(K * bs * C2F_SLABS),
-                     dim3(FBLK), 0, s, a1, w2t, b2, 64LL, 0LL, bs, K, p1,
-                     seeds_dev, offset, a2, pidx, m2);
+  hipLaunchKernelGGL(k_conv2_fwd_pool_mfma_mb<StepMetaDev>,
+                     dim3(K * bs * C2F_SLABS), dim3(FBLK), 0, s, a1, w2t, b2,
+                     64LL, 0LL, bs, K, p1,
+                     StepMetaDev{nullptr, nullptr, nullptr, seeds_dev, 0},
+                     offset, a2, pidx, m2);
 }
 void launch_pool_drop_bwd_bias(const float* da2, const unsigned char* pidx,
                                const unsigned char* m2, int bs, int K,
@@ -2493,22 +2353,18 @@ void launch_conv2_bwd_w_mfma(const float* dz2, const float* a1, int bs, int K,
                      s, dz2, a1, bs, K, slab);
   conv2_bwd_w_tail(dz2, slab, bs, K, dw2, db2, s);
 }
-// the seed arrives by value, so the fold runs the per-client wrapper once
-// per client (every client draws from the same seed)
+// the seed arrives by value (the fold's DEV = false form): every client
+// draws from the same seed
 void launch_fc1_fwd_mfma(const float* a2, const float* w3, const float* b3,
                          int bs, int K, float p2, unsigned long long seed,
                          unsigned long long offset, float* slab, float* z3,
                          float* a3, unsigned char* m3, hipStream_t s) {
   hipLaunchKernelGGL(k_fc1_fwd_mfma_mb, dim3(K * FC1_SPLIT), dim3(FBLK), 0, s,
                      a2, w3, W3N, 0LL, bs, K, slab);
-  for (int k = 0; k < K; ++k)
-    hipLaunchKernelGGL(k_fc1_fwd_reduce,
-                       dim3((bs * 128 + FC1R_BLK - 1) / FC1R_BLK),
-                       dim3(FC1R_BLK), 0, s,
-                       slab + (long long)k * FC1_SPLIT * bs * 128,
-                       b3 + k * 128, bs, p2, seed, offset,
-                       z3 + k * bs * 128, a3 + k * bs * 128,
-                       m3 + k * bs * 128);
+  hipLaunchKernelGGL(k_fc1_fwd_reduce_mb<false>,
+                     dim3((K * bs * 128 + FC1R_BLK - 1) / FC1R_BLK),
+                     dim3(FC1R_BLK), 0, s, slab, b3, 128LL, 0LL, bs, K, p2,
+                     nullptr, seed, offset, z3, a3, m3);
 }
 void launch_fc1_bwd_w_mfma(const float* dz3, const float* a2, int bs, int K,
                            float* dw3, float* db3, hipStream_t s) {
@@ -2534,14 +2390,10 @@ void launch_fc1_fwd_mfma_bf16(const float* a2, const float* w3,
                               hipStream_t s) {
   hipLaunchKernelGGL(k_fc1_fwd_mfma_mb_bf16, dim3(K * FC1B_SPLIT), dim3(FBLK),
                      0, s, a2, w3, W3N, 0LL, bs, K, slab);
-  for (int k = 0; k < K; ++k)
-    hipLaunchKernelGGL(k_fc1_fwd_reduce_bf16,
-                       dim3((bs * 128 + FC1R_BLK - 1) / FC1R_BLK),
-                       dim3(FC1R_BLK), 0, s,
-                       slab + (long long)k * FC1B_SPLIT * bs * 128,
-                       b3 + k * 128, bs, p2, seed, offset,
-                       z3 + k * bs * 128, a3 + k * bs * 128,
-                       m3 + k * bs * 128);
+  hipLaunchKernelGGL(k_fc1_fwd_reduce_mb_bf16<false>,
+                     dim3((K * bs * 128 + FC1R_BLK - 1) / FC1R_BLK),
+                     dim3(FC1R_BLK), 0, s, slab, b3, 128LL, 0LL, bs, K, p2,
+                     nullptr, seed, offset, z3, a3, m3);
 }
 // this kernel reads w2 and b2 through ONE stack pointer: w2b2 is K blocks
 // of [w2 (18432) | b2 (64)]

@@ -31,16 +31,35 @@ inline CnnOffsets cnn_offsets(int C) {
 // are the seams between blocks.  Exported as _C.CONV2_FWD_SLAB_ROWS.
 #define CONV2_FWD_SLAB_ROWS 4
 
-// per-client CNN workspace, laid out inside one float buffer by the
-// binding (sizes for B rows)
+// CNN workspace of G = K * bs rows over K clients (K = 1: the per-client
+// drivers), laid out inside the caller's buffers by the one slicer in
+// bindings.cpp
 struct CnnWorkspace {
   float *xb, *a1, *r2, *a2, *z3, *a3, *dlogits, *dz3, *da2, *dz2, *dz1;
-  float *wsl;  // split-K partial slab (B*18432 floats), shared fwd/bwd
-  float *w2t, *w2rot;  // per-batch W2 fragment layouts (18432 floats each)
-  int *yb;
+  float *wsl;  // split-K partial slab (G*18432 floats), shared fwd/bwd
+  float *w2t, *w2rot;  // per-step W2 fragment layouts (K*18432 floats each)
+  int *yb;             // G labels, -1 = inactive row
   unsigned char *pidx, *m2, *m3;
+  // K = 1 drivers only (their bindings set these): the two-stage
+  // launch_sum_sumsq2 partials and its 2-double result
   double *red_partials, *red_acc;
 };
+
+// element counts of that workspace: what the slicer checks and what the
+// Python drivers allocate (_C.cnn_workspace_sizes)
+struct CnnWorkspaceSizes {
+  long long n_float, n_int, n_byte;
+};
+
+inline CnnWorkspaceSizes cnn_workspace_sizes(long long G, long long K,
+                                             long long C) {
+  CnnWorkspaceSizes z;
+  z.n_float = G * (784 + 2 * 21632 + 2 * 36864 + 2 * 9216 + 3 * 128 + 18432
+                   + C) + K * 2 * 18432;
+  z.n_int = G;
+  z.n_byte = G * (2 * 9216 + 128);
+  return z;
+}
 
 // DGA end-of-round tail (k_dga_normsq_mb / k_dga_accum_mb): how client
 // k's aggregation weight is formed on the device.  ``mode`` selects
@@ -160,11 +179,7 @@ void launch_cnn_round_mega(
     const float* weights_dev, const long long* seeds_dev,
     int K, int bs, int C,
     const float* server_params, float* params_stack, float* grads_stack,
-    float* round_accum,
-    float* xb, float* a1, float* r2, float* a2, float* z3, float* a3,
-    float* dlogits, float* dz3, float* da2, float* dz2, float* dz1,
-    float* w2t_stack, float* w2rot_stack, float* slab,
-    int* yb, unsigned char* pidx, unsigned char* m2, unsigned char* m3,
+    float* round_accum, CnnWorkspace ws,
     double* acc2k,                      // 2K doubles; 3K when mu > 0
     const float* lr_t, float max_norm, float p1, float p2,
     float* stats_out, float* loss_out, hipStream_t s, int use_bf16,

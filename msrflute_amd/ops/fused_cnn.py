@@ -73,13 +73,10 @@ class FusedCNNEpoch:
         self.use_bf16 = bool(use_bf16)
         dev = arena.device
         B = self.bs
-        n_float = B * (784 + 21632 + 36864 + 9216 + 128 + 128 + self.C
-                       + 128 + 9216 + 36864 + 21632
-                       + 18432) + 2 * 18432  # + split-K slab + W2 layouts
+        n_float, n_int, n_byte = _C.cnn_workspace_sizes(B, 1, self.C)
         self.work_f = torch.empty(n_float, dtype=torch.float32, device=dev)
-        self.work_i = torch.empty(B, dtype=torch.int32, device=dev)
-        self.work_b = torch.empty(B * (9216 * 2 + 128), dtype=torch.uint8,
-                                  device=dev)
+        self.work_i = torch.empty(n_int, dtype=torch.int32, device=dev)
+        self.work_b = torch.empty(n_byte, dtype=torch.uint8, device=dev)
         self.work_d = torch.empty(2 * 2048 + 2, dtype=torch.float64,
                                   device=dev)
         self.lr_t = torch.zeros(1, dtype=torch.float32, device=dev)
@@ -171,18 +168,15 @@ class MegaRound:
         k = min(self.k_cap, max(8, K))
         dev = self.arena.device
         P = self.arena.total
-        G = k * self.bs
-        per_row = (784 + 21632 + 36864 + 9216 + 128 + 128 + self.C
-                   + 128 + 9216 + 36864 + 21632 + 18432)
+        n_float, n_int, n_byte = _C.cnn_workspace_sizes(k * self.bs, k,
+                                                        self.C)
         self.params_stack = torch.empty(k * P, dtype=torch.float32,
                                         device=dev)
         self.grads_stack = torch.empty(k * P, dtype=torch.float32,
                                        device=dev)
-        self.work_f = torch.empty(G * per_row + k * 36864,
-                                  dtype=torch.float32, device=dev)
-        self.work_i = torch.empty(G, dtype=torch.int32, device=dev)
-        self.work_b = torch.empty(G * (9216 * 2 + 128), dtype=torch.uint8,
-                                  device=dev)
+        self.work_f = torch.empty(n_float, dtype=torch.float32, device=dev)
+        self.work_i = torch.empty(n_int, dtype=torch.int32, device=dev)
+        self.work_b = torch.empty(n_byte, dtype=torch.uint8, device=dev)
         # per client: clip sum, sumsq (+ FedProx: sum (w - w_g)^2)
         self.work_d = torch.empty(3 * k, dtype=torch.float64, device=dev)
         self.loss_out = torch.zeros(k, dtype=torch.float32, device=dev)
