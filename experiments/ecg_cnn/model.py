@@ -13,6 +13,7 @@ from torch import nn
 from torch.nn import functional as F
 
 from msrflute_amd.core.model import BaseModel
+from msrflute_amd.ops.lstm import FusedLSTM
 from msrflute_amd.utils import to_device
 
 
@@ -44,7 +45,9 @@ class ECGNet(nn.Module):
         super().__init__()
         self.conv1 = ConvSkipBlock(input_size, hid_size, kernel_size)
         self.conv2 = ConvSkipBlock(hid_size, hid_size // 2, kernel_size)
-        self.lstm = nn.LSTM(hid_size // 2, lstm_hidden, batch_first=True)
+        # nn.LSTM's parameter names and init draws; on the GPU the fused
+        # recurrence kernels (hidden 64: W_hh in registers), nn.LSTM on CPU
+        self.lstm = FusedLSTM(hid_size // 2, lstm_hidden)
         self.attn = nn.Linear(lstm_hidden, lstm_hidden, bias=False)
         self.fc = nn.Linear(lstm_hidden, n_classes)
 

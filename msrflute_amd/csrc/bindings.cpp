@@ -389,15 +389,76 @@ static bool lstm_w_is_bf16(const torch::Tensor& w, const char* layout) {
   return true;
 }
 
+// Hidden sizes 64 and 128 (k_lstm_seq_small_*): fp32 only, forward on the
+// unpacked [K, 4H, H] stack, backward on its transpose [K, H, 4H].
+static bool lstm_small_h(const torch::Tensor& t) {
+  return t.dim() == 3 && (t.size(2) == 4 * 64 || t.size(2) == 4 * 128);
+}
+
+static long long lstm_small_clients(const torch::Tensor& w, long long R,
+                                    int64_t rows_per_client, long long d1,
+                                    long long d2, const char* layout) {
+  check_flat(w, "w_hh_stack");
+  TORCH_CHECK(rows_per_client > 0 && R % rows_per_client == 0);
+  long long K = R / rows_per_client;
+  TORCH_CHECK(w.dim() == 3 && w.size(0) == K && w.size(1) == d1 &&
+              w.size(2) == d2, "w_hh_stack must be float32 ", layout);
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(w.data_ptr()) % 16 == 0,
+              "w_hh_stack must be 16-byte aligned");
+  return K;
+}
+
+static std::vector<torch::Tensor> lstm_seq_small_fwd(
+    const torch::Tensor& xp, const torch::Tensor& w,
+    int64_t rows_per_client) {
+  long long R = xp.size(0), T = xp.size(1), H = xp.size(2) / 4;
+  lstm_small_clients(w, R, rows_per_client, 4 * H, H,
+                     "[K, 4H, H] for hidden sizes 64 and 128");
+  auto h_seq = torch::empty({R, T, H}, xp.options());
+  auto gates = torch::empty({R, T, 4 * H}, xp.options());
+  auto c_seq = torch::empty({R, T, H}, xp.options());
+  if (R > 0 && T > 0)
+    launch_lstm_seq_small_fwd((int)H, xp.data_ptr<float>(),
+                              w.data_ptr<float>(), h_seq.data_ptr<float>(),
+                              gates.data_ptr<float>(),
+                              c_seq.data_ptr<float>(), (int)R,
+                              (int)rows_per_client, (int)T, cur_stream());
+  return {h_seq, gates, c_seq};
+}
+
+static torch::Tensor lstm_seq_small_bwd(const torch::Tensor& gates,
+                                        const torch::Tensor& c_seq,
+                                        const torch::Tensor& w_t,
+                                        const torch::Tensor& dh_out,
+                                        int64_t rows_per_client) {
+  long long R = gates.size(0), T = gates.size(1), H = gates.size(2) / 4;
+  lstm_small_clients(w_t, R, rows_per_client, H, 4 * H,
+                     "[K, H, 4H] (ops/lstm._pack_bwd_small) for hidden "
+                     "sizes 64 and 128");
+  TORCH_CHECK(c_seq.numel() == R * T * H && dh_out.numel() == R * T * H,
+              "c_seq and dh_out must be [R, T, H]");
+  auto dg = torch::empty_like(gates);
+  if (R > 0 && T > 0)
+    launch_lstm_seq_small_bwd((int)H, gates.data_ptr<float>(),
+                              c_seq.data_ptr<float>(),
+                              w_t.data_ptr<float>(),
+                              dh_out.data_ptr<float>(), dg.data_ptr<float>(),
+                              (int)R, (int)rows_per_client, (int)T,
+                              cur_stream());
+  return dg;
+}
+
 std::vector<torch::Tensor> lstm_seq_fwd(torch::Tensor xp,
                                         torch::Tensor w_packed_stack,
                                         int64_t rows_per_client) {
   check_flat(xp, "xp");
+  if (lstm_small_h(xp))
+    return lstm_seq_small_fwd(xp, w_packed_stack, rows_per_client);
   bool bf16 = lstm_w_is_bf16(w_packed_stack,
                              "[K, 256/8, 4*256, 8] (ops/lstm._pack_fwd_bf16)");
   TORCH_CHECK(xp.dim() == 3 && xp.size(2) == 4 * 256,
-              "fused LSTM supports hidden size 256: xp must be "
-              "[R, T, 4*256]");
+              "fused LSTM supports hidden sizes 64, 128 and 256: xp must "
+              "be [R, T, 4*H]");
   long long R = xp.size(0), T = xp.size(1);
   TORCH_CHECK(rows_per_client > 0 && R % rows_per_client == 0);
   long long K = R / rows_per_client;
@@ -427,9 +488,17 @@ torch::Tensor lstm_seq_bwd(torch::Tensor gates, torch::Tensor c_seq,
                            torch::Tensor w_packed_stack,
                            torch::Tensor dh_out, int64_t rows_per_client) {
   check_flat(gates, "gates"); check_flat(c_seq, "c_seq");
+  if (lstm_small_h(gates)) {
+    check_flat(dh_out, "dh_out");
+    return lstm_seq_small_bwd(gates, c_seq, w_packed_stack, dh_out,
+                              rows_per_client);
+  }
   bool bf16 = lstm_w_is_bf16(w_packed_stack,
                              "[K, 4*256/8, 256, 8] (ops/lstm._pack_bwd_bf16)");
   check_flat(dh_out, "dh_out");
+  TORCH_CHECK(gates.dim() == 3 && gates.size(2) == 4 * 256,
+              "fused LSTM supports hidden sizes 64, 128 and 256: gates "
+              "must be [R, T, 4*H]");
   long long R = gates.size(0), T = gates.size(1);
   TORCH_CHECK(rows_per_client > 0 && R % rows_per_client == 0);
   long long K = R / rows_per_client;

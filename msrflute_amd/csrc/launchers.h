@@ -137,6 +137,18 @@ void launch_lstm_seq_bwd_bf16(const float* gates, const float* c_seq,
                               const unsigned short* w_hh_stack,
                               const float* dh_out, float* dg_pre, int R,
                               int rows_per_client, int T, hipStream_t s);
+// hidden sizes 64 and 128: W_hh resident in registers, one block of 4H
+// threads per row.  Forward reads the unpacked [K, 4H, H] stack, backward
+// its per-client transpose [K, H, 4H] (ops/lstm._pack_bwd_small).  H is
+// 64 or 128 and R, T >= 1 (checked by the bindings).
+void launch_lstm_seq_small_fwd(int H, const float* xp,
+                               const float* w_hh_stack, float* h_seq,
+                               float* gates, float* c_seq, int R,
+                               int rows_per_client, int T, hipStream_t s);
+void launch_lstm_seq_small_bwd(int H, const float* gates, const float* c_seq,
+                               const float* w_hh_t_stack,
+                               const float* dh_out, float* dg_pre, int R,
+                               int rows_per_client, int T, hipStream_t s);
 
 // gru_seq.hip
 void launch_gru_seq_fwd(const float* gi, const float* whh_t,

@@ -283,7 +283,272 @@ void k_lstm_seq_bwd(const float* __restrict__ gates,
   }
 }
 
+// ---------------------------------------------------------------------
+// Small hidden sizes (H = 64, 128): W_hh in registers.
+//
+// A gate column's W_hh row is H floats, so a thread holds ALL of it for
+// the T steps and no weight is loaded inside the t loop.  One block of 4H
+// threads per row, QUAD layout: thread tid owns hidden unit h = tid >> 2
+// and gate q = tid & 3, so the four lanes of a quad hold i, f, g, o of
+// one h and exchange them with quad shuffles — no activation array in
+// LDS, one barrier per step.  c (forward), dc and dh_rec (backward) are
+// carried redundantly by the four lanes of a quad; they run the same
+// operations on the same values, so the copies are bit-equal.
+// Row r uses client r / rows_per_client's weights, as above.
+
+// These kernels are compiled without gfx950's packed fp32 VALU ops (device
+// pass only; the host pass does not know the feature).  Only the backward
+// needs it: there the vectoriser pairs part of the four-chain dot into 22
+// v_pk_fma_f32 (+ one v_pk_add, one v_pk_mul) and pays for the aligned
+// register pairs with 63 more v_mov_b32 (83 against 20), and 5 / 2 more
+// VGPRs (110 / 171 against 105 / 169 at H = 64 / 128).  Scalar code is
+// the shorter kernel.  Which form is faster on the GPU has NOT been
+// measured.  The forward compiles to the same instructions either way and
+// carries the attribute only so that tanh_s is the same code, bit for
+// bit, in the kernel that saves the states and the one that reads them.
+// A function with its own target features cannot inline the device
+// library or the HIP headers, so the two transcendentals, the quad
+// exchange and the barrier are written here on builtins, always inlined.
+#if defined(__HIP_DEVICE_COMPILE__)
+#define LSTM_SCALAR_F32 __attribute__((target("no-packed-fp32-ops")))
+#else
+#define LSTM_SCALAR_F32
+#endif
+#define LSTM_INL __device__ __forceinline__ LSTM_SCALAR_F32
+
+// e^x for |x| <= 87 (clamped: every result stays a finite normal):
+// v_exp_f32 (1 ulp) on x * log2(e), with the rounding error of that
+// product, which |x| would amplify, put back to first order.  The clamp
+// is two compare-and-selects, not fmin / fmax: v_min_f32 / v_max_f32
+// return the operand that is not a NaN, and a NaN pre-activation (a
+// client that diverged upstream) has to come out of sig_s and tanh_s as
+// NaN, as it does out of nn.LSTM and the H = 256 kernels.
+LSTM_INL float exp_s(float x) {
+  x = x < -87.f ? -87.f : x;
+  x = x > 87.f ? 87.f : x;
+  const float l2e_hi = 1.44269502e+0f, l2e_lo = 1.92596299e-8f;
+  float t = x * l2e_hi;
+  float r = __builtin_fmaf(x, l2e_lo, __builtin_fmaf(x, l2e_hi, -t));
+  float e = __builtin_amdgcn_exp2f(t);
+  return __builtin_fmaf(e, r * 0.693147181f, e);
+}
+
+LSTM_INL float sig_s(float x) { return 1.f / (1.f + exp_s(-x)); }
+
+// tanh: below 0.625 an odd polynomial x + x^3 p(x^2); above it
+// 1 - 2/(e^2x + 1), where the subtraction no longer cancels (it
+// saturates to 1 through the clamp of exp_s).  p is the degree-4
+// least-squares fit of (tanh(x)/x - 1)/x^2 in t = x^2 at 400 Chebyshev
+// nodes of [0, 0.625^2], computed in float64 (numpy
+// Chebyshev.fit -> power basis) and rounded to float32; evaluated as
+// below in float32 its largest relative error over the interval is
+// 1.42 * 2^-24.  tests/test_lstm_small_gpu.py walks the gate inputs
+// across the branch point and into saturation against float64.
+LSTM_INL float tanh_s(float y) {
+  float x = __builtin_fabsf(y);
+  float t = x * x;
+  float p = -0x1.9017fep-8f;
+  p = __builtin_fmaf(p, t, 0x1.581fa6p-6f);
+  p = __builtin_fmaf(p, t, -0x1.b928e0p-5f);
+  p = __builtin_fmaf(p, t, 0x1.110e2ep-3f);
+  p = __builtin_fmaf(p, t, -0x1.555552p-2f);
+  float small = __builtin_fmaf(t, x * p, x);
+  float big = 1.f - 2.f / (exp_s(2.f * x) + 1.f);
+  return __builtin_copysignf(x < 0.625f ? small : big, y);
+}
+
+// lane L of the caller's quad (DPP quad_perm [L, L, L, L]), and the lane
+// at distance 1 / 2 inside it ([1, 0, 3, 2] / [2, 3, 0, 1]); every lane of
+// the block is active wherever these are called
+template <int CTRL>
+LSTM_INL float quad_perm(float v) {
+  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(
+      0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, false));
+}
+template <int L>
+LSTM_INL float quad_lane(float v) { return quad_perm<L * 0x55>(v); }
+
+// __syncthreads(), spelled out for the same reason
+LSTM_INL void block_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+  __builtin_amdgcn_s_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+}
+
+// xp [R, T, 4H]; w_hh_stack [K, 4H, H] UNPACKED (row j = q*H + h is
+// contiguous); outputs as k_lstm_seq_fwd.
+template <int H>
+__global__ __launch_bounds__(4 * H) LSTM_SCALAR_F32
+void k_lstm_seq_small_fwd(const float* __restrict__ xp,
+                          const float* __restrict__ w_hh_stack,
+                          float* __restrict__ h_seq,
+                          float* __restrict__ gates,
+                          float* __restrict__ c_seq, int rows_per_client,
+                          int T) {
+  __shared__ float4 h_prev[2][H / 4];    // double-buffered h_{t-1}
+  const int tid = threadIdx.x;
+  const int h = tid >> 2, q = tid & 3;
+  const int j = q * H + h;               // gate column, torch's order
+  const long long b = blockIdx.x;
+  const float4* wp = reinterpret_cast<const float4*>(
+      w_hh_stack + ((b / rows_per_client) * 4 * H + j) * H);
+  float4 w[H / 4];
+  #pragma unroll
+  for (int kk = 0; kk < H / 4; ++kk) w[kk] = wp[kk];
+  if (tid < H) reinterpret_cast<float*>(h_prev[0])[tid] = 0.f;
+  const float* xr = xp + b * T * 4 * H + j;
+  float* gr = gates + b * T * 4 * H + j;
+  float* cr = c_seq + b * T * H + h;
+  float* hr = h_seq + b * T * H + h;
+  float c = 0.f;
+  float x = xr[0];
+  block_sync();
+  for (int t = 0; t < T; ++t) {
+    // the next step's projection is in flight during this step's dot
+    float xn = (t + 1 < T) ? xr[(long long)(t + 1) * 4 * H] : 0.f;
+    const float4* hp = h_prev[t & 1];
+    float s0 = x, s1 = 0.f, s2 = 0.f, s3 = 0.f;
+    #pragma unroll
+    for (int kk = 0; kk < H / 4; ++kk) {
+      float4 hv = hp[kk];                // same address in every lane
+      s0 = fmaf(w[kk].x, hv.x, s0);
+      s1 = fmaf(w[kk].y, hv.y, s1);
+      s2 = fmaf(w[kk].z, hv.z, s2);
+      s3 = fmaf(w[kk].w, hv.w, s3);
+    }
+    float s = (s0 + s1) + (s2 + s3);
+    float act = (q == 2) ? tanh_s(s) : sig_s(s);
+    gr[(long long)t * 4 * H] = act;
+    float i = quad_lane<0>(act), f = quad_lane<1>(act);
+    float g = quad_lane<2>(act), o = quad_lane<3>(act);
+    c = f * c + i * g;
+    float hn = o * tanh_s(c);
+    if (q == 0) {
+      cr[(long long)t * H] = c;
+      hr[(long long)t * H] = hn;
+      reinterpret_cast<float*>(h_prev[(t + 1) & 1])[h] = hn;
+    }
+    x = xn;
+    // step t + 1 reads the half written here and writes the half read
+    // here, which every thread has finished with once it arrives
+    block_sync();
+  }
+}
+
+// gates / c_seq / dh_out / dg_pre as k_lstm_seq_bwd.  w_hh_t_stack
+// [K, H, 4H] = W_hh transposed per client (ops/lstm._pack_bwd_small):
+// thread (q, h) keeps W_hh[q*H + j', h], j' = 0 .. H-1, which is the
+// contiguous run [h][q*H ..] there.
+template <int H>
+__global__ __launch_bounds__(4 * H) LSTM_SCALAR_F32
+void k_lstm_seq_small_bwd(const float* __restrict__ gates,
+                          const float* __restrict__ c_seq,
+                          const float* __restrict__ w_hh_t_stack,
+                          const float* __restrict__ dh_out,
+                          float* __restrict__ dg_pre, int rows_per_client,
+                          int T) {
+  // quarter q of the gate gradients starts at float4 q * QS: the pad
+  // puts the four quarters a wave reads at once on different banks
+  constexpr int QS = H / 4 + 1;
+  __shared__ float4 dg_l[2][4 * QS];
+  const int tid = threadIdx.x;
+  const int h = tid >> 2, q = tid & 3;
+  const int j = q * H + h;
+  const long long b = blockIdx.x;
+  const float4* wp = reinterpret_cast<const float4*>(
+      w_hh_t_stack + ((b / rows_per_client) * H + h) * 4 * H + q * H);
+  float4 w[H / 4];
+  #pragma unroll
+  for (int kk = 0; kk < H / 4; ++kk) w[kk] = wp[kk];
+  const float* gr = gates + b * T * 4 * H + j;
+  float* dgr = dg_pre + b * T * 4 * H + j;
+  const float* cr = c_seq + b * T * H + h;
+  const float* dhr = dh_out + b * T * H + h;
+  float dc = 0.f, dh_rec = 0.f;
+  // step t needs act_t, c_t, c_{t-1}, dh_t: loaded one step ahead
+  float act = gr[(long long)(T - 1) * 4 * H];
+  float ct = cr[(long long)(T - 1) * H];
+  float cprev = (T > 1) ? cr[(long long)(T - 2) * H] : 0.f;
+  float dho = dhr[(long long)(T - 1) * H];
+  for (int t = T - 1; t >= 0; --t) {
+    float act_n = 0.f, dho_n = 0.f, c_n = 0.f;
+    if (t > 0) {
+      act_n = gr[(long long)(t - 1) * 4 * H];
+      dho_n = dhr[(long long)(t - 1) * H];
+    }
+    if (t > 1) c_n = cr[(long long)(t - 2) * H];
+    float i = quad_lane<0>(act), f = quad_lane<1>(act);
+    float g = quad_lane<2>(act), o = quad_lane<3>(act);
+    float tc = tanh_s(ct);
+    float dh = dho + dh_rec;
+    dc = dc + dh * o * (1.f - tc * tc);
+    float d;
+    if (q == 0) d = dc * g * i * (1.f - i);
+    else if (q == 1) d = dc * cprev * f * (1.f - f);
+    else if (q == 2) d = dc * i * (1.f - g * g);
+    else d = dh * tc * o * (1.f - o);
+    dc = dc * f;
+    dgr[(long long)t * 4 * H] = d;
+    float4* dgb = dg_l[t & 1];
+    reinterpret_cast<float*>(dgb + q * QS)[h] = d;
+    // the only barrier of the step: the next step writes the other
+    // half, and the one after that comes behind the next barrier
+    block_sync();
+    const float4* dq = dgb + q * QS;
+    float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
+    #pragma unroll
+    for (int kk = 0; kk < H / 4; ++kk) {
+      float4 dv = dq[kk];
+      s0 = fmaf(w[kk].x, dv.x, s0);
+      s1 = fmaf(w[kk].y, dv.y, s1);
+      s2 = fmaf(w[kk].z, dv.z, s2);
+      s3 = fmaf(w[kk].w, dv.w, s3);
+    }
+    float s = (s0 + s1) + (s2 + s3);
+    // W_hh^T dg for unit h = the quad's four quarter sums; the two
+    // exchanges add the same pairs in every lane
+    s += quad_perm<0xB1>(s);
+    s += quad_perm<0x4E>(s);
+    dh_rec = s;
+    act = act_n; dho = dho_n; ct = cprev; cprev = c_n;
+  }
+}
+
+template <int H>
+static void lstm_small_fwd(const float* xp, const float* w, float* h_seq,
+                           float* gates, float* c_seq, int R, int rpc, int T,
+                           hipStream_t s) {
+  hipLaunchKernelGGL(k_lstm_seq_small_fwd<H>, dim3(R), dim3(4 * H), 0, s, xp,
+                     w, h_seq, gates, c_seq, rpc, T);
+}
+
+template <int H>
+static void lstm_small_bwd(const float* gates, const float* c_seq,
+                           const float* w_t, const float* dh_out,
+                           float* dg_pre, int R, int rpc, int T,
+                           hipStream_t s) {
+  hipLaunchKernelGGL(k_lstm_seq_small_bwd<H>, dim3(R), dim3(4 * H), 0, s,
+                     gates, c_seq, w_t, dh_out, dg_pre, rpc, T);
+}
+
 extern "C" {
+
+// H must be 64 or 128 (checked by the bindings); R, T >= 1
+void launch_lstm_seq_small_fwd(int H, const float* xp,
+                               const float* w_hh_stack, float* h_seq,
+                               float* gates, float* c_seq, int R,
+                               int rows_per_client, int T, hipStream_t s) {
+  (H == 64 ? lstm_small_fwd<64> : lstm_small_fwd<128>)(
+      xp, w_hh_stack, h_seq, gates, c_seq, R, rows_per_client, T, s);
+}
+
+void launch_lstm_seq_small_bwd(int H, const float* gates, const float* c_seq,
+                               const float* w_hh_t_stack,
+                               const float* dh_out, float* dg_pre, int R,
+                               int rows_per_client, int T, hipStream_t s) {
+  (H == 64 ? lstm_small_bwd<64> : lstm_small_bwd<128>)(
+      gates, c_seq, w_hh_t_stack, dh_out, dg_pre, R, rows_per_client, T, s);
+}
 
 void launch_lstm_seq_fwd(const float* xp, const float* w_hh_t_stack,
                          float* h_seq, float* gates, float* c_seq, int R,

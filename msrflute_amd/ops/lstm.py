@@ -8,7 +8,7 @@ launch per layer (forward and BPTT backward), and the weight gradients
 are two GEMMs — ~25 graph-capturable nodes per batch.
 
 Parameter names match ``nn.LSTM`` (``weight_ih_l{k}`` …) so checkpoints
-interchange; on CPU (or hidden sizes other than 256) an unregistered
+interchange; on CPU (or hidden sizes other than 64, 128, 256) an unregistered
 ``nn.LSTM`` sharing the SAME Parameter objects runs the reference path.
 """
 
@@ -60,6 +60,28 @@ def _pack_bwd_bf16(w_hh):
     return _to_bf16(w_hh.reshape(*lead, H4 // 8, 8, H).transpose(-1, -2))
 
 
+def _pack_fwd_small(w_hh):
+    """Hidden sizes 64 / 128: the forward kernel reads row j of the
+    unpacked [..., 4H, H] stack, which is already contiguous."""
+    return w_hh.contiguous()
+
+
+def _pack_bwd_small(w_hh):
+    """[..., 4H, H] -> [..., H, 4H]: element (h, j) = W_hh[j, h], so the
+    H weights thread (q, h) keeps, W_hh[qH .. qH+H-1, h], are one run."""
+    return w_hh.transpose(-1, -2).contiguous()
+
+
+def _packs(hidden_size, bf16_weights):
+    """(forward, backward) weight layouts of the kernel pair that serves
+    ``hidden_size``; the small-H pair has no bf16 form (nothing streams)."""
+    if hidden_size != 256:
+        return _pack_fwd_small, _pack_bwd_small
+    if bf16_weights:
+        return _pack_fwd_bf16, _pack_bwd_bf16
+    return _pack_fwd, _pack_bwd
+
+
 class _LSTMSeq(torch.autograd.Function):
     """One LSTM layer's recurrence over xp [R, T, 4H] with K-stacked
     hidden weights w_hh_stack [K, 4H, H]: row r uses client
@@ -72,7 +94,7 @@ class _LSTMSeq(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, xp, w_hh_stack, rows_per_client, bf16_weights=False):
-        pack = _pack_fwd_bf16 if bf16_weights else _pack_fwd
+        pack = _packs(w_hh_stack.shape[-1], bf16_weights)[0]
         h_seq, gates, c_seq = _C.lstm_seq_fwd(
             xp.contiguous(), pack(w_hh_stack), rows_per_client)
         ctx.save_for_backward(gates, c_seq, w_hh_stack, h_seq)
@@ -84,7 +106,7 @@ class _LSTMSeq(torch.autograd.Function):
     def backward(ctx, dh):
         gates, c_seq, w_hh_stack, h_seq = ctx.saved_tensors
         rpc = ctx.rows_per_client
-        pack = _pack_bwd_bf16 if ctx.bf16_weights else _pack_bwd
+        pack = _packs(w_hh_stack.shape[-1], ctx.bf16_weights)[1]
         dg = _C.lstm_seq_bwd(gates, c_seq, pack(w_hh_stack),
                              dh.contiguous(), rpc)
         R, T, H = h_seq.shape
@@ -106,7 +128,12 @@ class FusedLSTM(nn.Module):
     ``bf16_recurrent`` (off by default; ``client_config.mixed_precision:
     bf16`` sets it on client models) makes TRAINING-mode calls of the
     fused path stream W_hh as bf16 (see ``_LSTMSeq``).  Evaluation stays
-    fp32, so metrics are a function of the master weights alone."""
+    fp32, so metrics are a function of the master weights alone.
+
+    Hidden sizes 64, 128 and 256 run the fused kernels; any other size
+    runs ``nn.LSTM``.  At 64 and 128 W_hh lives in registers for the whole
+    sequence (``k_lstm_seq_small_*``): nothing streams, so
+    ``bf16_recurrent`` is ignored there and the fp32 kernels run."""
 
     bf16_recurrent = False
 
@@ -126,7 +153,7 @@ class FusedLSTM(nn.Module):
         object.__setattr__(self, "_fallback", fallback)
 
     def _use_fused(self, x):
-        return (x.is_cuda and HAS_EXT and self.hidden_size == 256
+        return (x.is_cuda and HAS_EXT and self.hidden_size in (64, 128, 256)
                 and x.dtype == torch.float32)
 
     def forward(self, x, hx=None):
