@@ -24,7 +24,14 @@ from msrflute_amd.utils import to_device
 
 
 class GRUCellSeq(nn.Module):
-    """GRU recurrence over a full sequence with precomputed input gates."""
+    """GRU recurrence over a full sequence with precomputed input gates.
+
+    ``bf16_recurrent`` (off by default; ``client_config.mixed_precision:
+    bf16`` sets it on client models) makes TRAINING-mode calls of the fused
+    path stream ``w_hh`` stored as bf16 with fp32 arithmetic.  Evaluation
+    stays fp32 on the master weights."""
+
+    bf16_recurrent = False
 
     def __init__(self, input_size, hidden_size):
         super().__init__()
@@ -38,7 +45,9 @@ class GRUCellSeq(nn.Module):
         from msrflute_amd.ops.lstm import fused_gru_available, fused_gru_seq
         if T > 0 and fused_gru_available(self.hidden_size, emb):
             # whole recurrence = ONE kernel launch (csrc/gru_seq.hip)
-            h_seq = fused_gru_seq(g_i, self.w_hh.weight, self.w_hh.bias)
+            h_seq = fused_gru_seq(
+                g_i, self.w_hh.weight, self.w_hh.bias,
+                bf16_weights=bool(self.bf16_recurrent and self.training))
             hiddens = torch.cat(
                 [emb.new_zeros(B, 1, self.hidden_size), h_seq], dim=1)
             return hiddens, h_seq[:, -1]

@@ -113,11 +113,12 @@ class ClientExecutor:
         self.model = make_model(self.model_config)
         self.arena = ParameterArena(self.model, bind_grads=True)
         if self.client_config.get("mixed_precision", "") == "bf16":
-            # client training streams the LSTM recurrent weights as bf16
-            # (fp32 masters and arithmetic; evaluation stays fp32)
-            from ..ops.lstm import FusedLSTM
+            # client training streams the LSTM / GRU recurrent weights as
+            # bf16 (fp32 masters and arithmetic; evaluation stays fp32).
+            # Keyed on the attribute: FusedLSTM has it, and so does the
+            # nlg_gru GRUCellSeq, whose model file is loaded dynamically
             for m in self.model.modules():
-                if isinstance(m, FusedLSTM):
+                if hasattr(type(m), "bf16_recurrent"):
                     m.bf16_recurrent = True
         # reusable fused optimizer (reset per client)
         opt_cfg = dict(self.client_config["optimizer_config"])

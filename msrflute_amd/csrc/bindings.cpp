@@ -520,22 +520,50 @@ torch::Tensor lstm_seq_bwd(torch::Tensor gates, torch::Tensor c_seq,
   return dg;
 }
 
-// fused GRU sequence recurrence (gru_seq.hip)
+// fused GRU sequence recurrence (gru_seq.hip).  The dtype of the packed
+// W_hh selects the instantiation, as for the LSTM: float32 groups of 4 or
+// bfloat16 groups of 8 (whose shape is checked: a transposed or fp32-shaped
+// bf16 pack would otherwise be read as the wrong weights).
+static bool gru_w_is_bf16(const torch::Tensor& w, const char* name,
+                          int64_t groups, int64_t cols, const char* layout) {
+  if (w.scalar_type() != torch::kBFloat16) {
+    check_flat(w, name);
+    return false;
+  }
+  TORCH_CHECK(w.is_cuda(), name, " must be on GPU");
+  TORCH_CHECK(w.is_contiguous() && w.dim() == 3 && w.size(0) == groups &&
+              w.size(1) == cols && w.size(2) == 8 &&
+              reinterpret_cast<uintptr_t>(w.data_ptr()) % 16 == 0,
+              "bf16 ", name, " must be a contiguous, 16-byte aligned pack ",
+              layout);
+  return true;
+}
+
 std::vector<torch::Tensor> gru_seq_fwd(torch::Tensor gi, torch::Tensor whh_t,
                                        torch::Tensor b_hh) {
-  check_flat(gi, "gi"); check_flat(whh_t, "whh_t"); check_flat(b_hh, "b_hh");
+  check_flat(gi, "gi"); check_flat(b_hh, "b_hh");
+  bool bf16 = gru_w_is_bf16(whh_t, "whh_t", 512 / 8, 3 * 512,
+                            "[512/8, 3*512, 8] (ops/lstm._gru_pack_fwd_bf16)");
   TORCH_CHECK(gi.dim() == 3 && gi.size(2) == 3 * 512 &&
               whh_t.numel() == 512 * 3 * 512,
               "fused GRU supports hidden size 512; pass W_hh "
-              "float4-packed [H/4, 3H, 4] (ops/lstm._GRUSeq)");
+              "float4-packed [H/4, 3H, 4] (ops/lstm._gru_pack_fwd)");
   long long B = gi.size(0), T = gi.size(1);
   auto h_seq = torch::empty({B, T, 512}, gi.options());
   auto gates = torch::empty({B, T, 3 * 512}, gi.options());
   auto ghn = torch::empty({B, T, 512}, gi.options());
-  launch_gru_seq_fwd(gi.data_ptr<float>(), whh_t.data_ptr<float>(),
-                     b_hh.data_ptr<float>(), h_seq.data_ptr<float>(),
-                     gates.data_ptr<float>(), ghn.data_ptr<float>(),
-                     (int)B, (int)T, cur_stream());
+  if (bf16)
+    launch_gru_seq_fwd_bf16(
+        gi.data_ptr<float>(),
+        static_cast<const unsigned short*>(whh_t.data_ptr()),
+        b_hh.data_ptr<float>(), h_seq.data_ptr<float>(),
+        gates.data_ptr<float>(), ghn.data_ptr<float>(), (int)B, (int)T,
+        cur_stream());
+  else
+    launch_gru_seq_fwd(gi.data_ptr<float>(), whh_t.data_ptr<float>(),
+                       b_hh.data_ptr<float>(), h_seq.data_ptr<float>(),
+                       gates.data_ptr<float>(), ghn.data_ptr<float>(),
+                       (int)B, (int)T, cur_stream());
   return {h_seq, gates, ghn};
 }
 
@@ -544,17 +572,26 @@ std::vector<torch::Tensor> gru_seq_bwd(torch::Tensor gates, torch::Tensor ghn,
                                        torch::Tensor w_hh,
                                        torch::Tensor dh_out) {
   check_flat(gates, "gates"); check_flat(ghn, "ghn");
-  check_flat(h_seq, "h_seq"); check_flat(w_hh, "w_hh");
-  check_flat(dh_out, "dh_out");
+  check_flat(h_seq, "h_seq"); check_flat(dh_out, "dh_out");
+  bool bf16 = gru_w_is_bf16(w_hh, "w_hh", 3 * 512 / 8, 512,
+                            "[3*512/8, 512, 8] (ops/lstm._gru_pack_bwd_bf16)");
   TORCH_CHECK(w_hh.numel() == 3 * 512 * 512,
               "gru_seq_bwd wants W_hh float4-packed [3H/4, H, 4]");
   long long B = gates.size(0), T = gates.size(1);
   auto dgi = torch::empty_like(gates);
   auto dgh = torch::empty_like(gates);
-  launch_gru_seq_bwd(gates.data_ptr<float>(), ghn.data_ptr<float>(),
-                     h_seq.data_ptr<float>(), w_hh.data_ptr<float>(),
-                     dh_out.data_ptr<float>(), dgi.data_ptr<float>(),
-                     dgh.data_ptr<float>(), (int)B, (int)T, cur_stream());
+  if (bf16)
+    launch_gru_seq_bwd_bf16(
+        gates.data_ptr<float>(), ghn.data_ptr<float>(),
+        h_seq.data_ptr<float>(),
+        static_cast<const unsigned short*>(w_hh.data_ptr()),
+        dh_out.data_ptr<float>(), dgi.data_ptr<float>(),
+        dgh.data_ptr<float>(), (int)B, (int)T, cur_stream());
+  else
+    launch_gru_seq_bwd(gates.data_ptr<float>(), ghn.data_ptr<float>(),
+                       h_seq.data_ptr<float>(), w_hh.data_ptr<float>(),
+                       dh_out.data_ptr<float>(), dgi.data_ptr<float>(),
+                       dgh.data_ptr<float>(), (int)B, (int)T, cur_stream());
   return {dgi, dgh};
 }
 

@@ -150,7 +150,8 @@ void launch_lstm_seq_small_bwd(int H, const float* gates, const float* c_seq,
                                const float* dh_out, float* dg_pre, int R,
                                int rows_per_client, int T, hipStream_t s);
 
-// gru_seq.hip
+// gru_seq.hip — packed W_hh of the one H = 512 model (fp32 groups of 4:
+// ops/lstm._gru_pack_fwd / _gru_pack_bwd)
 void launch_gru_seq_fwd(const float* gi, const float* whh_t,
                         const float* b_hh, float* h_seq, float* gates,
                         float* ghn, int B, int T, hipStream_t s);
@@ -158,6 +159,15 @@ void launch_gru_seq_bwd(const float* gates, const float* ghn,
                         const float* h_seq, const float* w_hh,
                         const float* dh_out, float* dgi, float* dgh,
                         int B, int T, hipStream_t s);
+// the same kernels on bf16-stored W_hh (8 k's per 16-byte group,
+// ops/lstm._gru_pack_fwd_bf16 / _gru_pack_bwd_bf16); all arithmetic fp32
+void launch_gru_seq_fwd_bf16(const float* gi, const unsigned short* whh_t,
+                             const float* b_hh, float* h_seq, float* gates,
+                             float* ghn, int B, int T, hipStream_t s);
+void launch_gru_seq_bwd_bf16(const float* gates, const float* ghn,
+                             const float* h_seq, const unsigned short* w_hh,
+                             const float* dh_out, float* dgi, float* dgh,
+                             int B, int T, hipStream_t s);
 
 // fused_cnn.hip — drivers.  mu > 0 (FedProx) makes the clip/SGD tail of
 // every step use g + mu (w - server) and adds 0.5 mu ||w - server||^2 to

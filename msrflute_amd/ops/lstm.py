@@ -171,31 +171,72 @@ class FusedLSTM(nn.Module):
         return h, None
 
 
+def _gru_pack_fwd(w_hh):
+    """[3H, H] -> float4-packed [H/4, 3H, 4]: element (kk, j, d) =
+    W_hh[j, 4kk+d] (the LSTM's _pack_fwd with 3H gate columns)."""
+    H3, H = w_hh.shape
+    return w_hh.t().reshape(H // 4, 4, H3).permute(0, 2, 1).contiguous()
+
+
+def _gru_pack_bwd(w_hh):
+    """[3H, H] -> float4-packed [3H/4, H, 4]: element (jg, h, d) =
+    W_hh[4jg+d, h]."""
+    H3, H = w_hh.shape
+    return w_hh.reshape(H3 // 4, 4, H).permute(0, 2, 1).contiguous()
+
+
+def _gru_pack_fwd_bf16(w_hh):
+    """[3H, H] -> bf16 [H/8, 3H, 8]: element (kk, j, d) =
+    bf16(W_hh[j, 8kk+d]) — one 16-byte load per 8 hidden units; element d
+    even is the low half of its 32-bit word."""
+    H3, H = w_hh.shape
+    return _to_bf16(w_hh.t().reshape(H // 8, 8, H3).permute(0, 2, 1))
+
+
+def _gru_pack_bwd_bf16(w_hh):
+    """[3H, H] -> bf16 [3H/8, H, 8]: element (jg, h, d) =
+    bf16(W_hh[8jg+d, h])."""
+    H3, H = w_hh.shape
+    return _to_bf16(w_hh.reshape(H3 // 8, 8, H).permute(0, 2, 1))
+
+
+def _gru_packs(bf16_weights):
+    """(forward, backward) weight layouts of the GRU kernel pair."""
+    if bf16_weights:
+        return _gru_pack_fwd_bf16, _gru_pack_bwd_bf16
+    return _gru_pack_fwd, _gru_pack_bwd
+
+
 class _GRUSeq(torch.autograd.Function):
     """Fused GRU sequence (csrc/gru_seq.hip) — reference cell semantics
-    (experiments/nlg_gru/model.py GRU2)."""
+    (experiments/nlg_gru/model.py GRU2).
+
+    ``bf16_weights``: both kernels read W_hh rounded to bf16 (packed anew
+    on every call — SGD moves the fp32 masters every step) and compute in
+    fp32, i.e. the recurrence evaluated at ``w_hh.bfloat16().float()``;
+    dW_hh and db_hh are the same fp32 GEMM and sum over the kernel's dgh
+    and land on the masters (straight-through)."""
 
     @staticmethod
-    def forward(ctx, gi, w_hh, b_hh):
-        # float4-packed layouts (see _pack_fwd/_pack_bwd; 3H gate blocks)
-        H3, H = w_hh.shape
-        w_p = w_hh.t().reshape(H // 4, 4, H3).permute(0, 2, 1).contiguous()
+    def forward(ctx, gi, w_hh, b_hh, bf16_weights=False):
+        pack = _gru_packs(bf16_weights)[0]
         h_seq, gates, ghn = _C.gru_seq_fwd(
-            gi.contiguous(), w_p, b_hh.contiguous())
+            gi.contiguous(), pack(w_hh), b_hh.contiguous())
         ctx.save_for_backward(gates, ghn, h_seq, w_hh)
+        ctx.bf16_weights = bf16_weights
         return h_seq
 
     @staticmethod
     def backward(ctx, dh):
         gates, ghn, h_seq, w_hh = ctx.saved_tensors
-        H3, H = w_hh.shape
-        w_pb = w_hh.reshape(H3 // 4, 4, H).permute(0, 2, 1).contiguous()
-        dgi, dgh = _C.gru_seq_bwd(gates, ghn, h_seq, w_pb, dh.contiguous())
+        pack = _gru_packs(ctx.bf16_weights)[1]
+        dgi, dgh = _C.gru_seq_bwd(gates, ghn, h_seq, pack(w_hh),
+                                  dh.contiguous())
         B, T, H = h_seq.shape
         h_prev = torch.cat([h_seq.new_zeros(B, 1, H), h_seq[:, :-1]], dim=1)
         dw_hh = dgh.reshape(-1, 3 * H).t().mm(h_prev.reshape(-1, H))
         db_hh = dgh.sum(dim=(0, 1))
-        return dgi, dw_hh, db_hh
+        return dgi, dw_hh, db_hh, None   # None: bf16_weights
 
 
 def fused_gru_available(hidden_size, x):
@@ -203,5 +244,5 @@ def fused_gru_available(hidden_size, x):
         and x.dtype == torch.float32
 
 
-def fused_gru_seq(gi, w_hh_weight, w_hh_bias):
-    return _GRUSeq.apply(gi, w_hh_weight, w_hh_bias)
+def fused_gru_seq(gi, w_hh_weight, w_hh_bias, bf16_weights=False):
+    return _GRUSeq.apply(gi, w_hh_weight, w_hh_bias, bool(bf16_weights))
