@@ -9,7 +9,15 @@ MI355X-native divergences: multi-head attention uses
 ``F.scaled_dot_product_attention`` (fused flash-style kernel on ROCm)
 instead of 4 einsum kernels; the embedding matrix is random-init frozen
 (no GloVe download offline — pass ``embedding_path`` to a local ``.npy``
-to load real vectors); metrics are computed in torch (no sklearn/nltk).
+to load real vectors); metrics are computed in torch (no sklearn/nltk);
+the user encoder's GRU over the last 20 clicks is ``FusedGRU`` (H = 400:
+the any-H fused recurrence, csrc/gru_seq_any.hip, one launch per
+direction instead of MIOpen's per-step RNN path; same parameter names and
+CPU results as ``nn.GRU``).
+
+The task runs the eager epoch: its batches carry a (click, sample) tuple
+under ``"x"``, so the trainer's probe in ``_run_train_epoch_graphed``
+(``torch.is_tensor(probe.get("x"))``) turns graph capture off for it.
 """
 
 import numpy as np
@@ -18,6 +26,7 @@ from torch import nn
 from torch.nn import functional as F
 
 from msrflute_amd.core.model import BaseModel
+from msrflute_amd.ops.lstm import FusedGRU
 from msrflute_amd.utils import to_device
 
 NPRATIO = 4
@@ -94,7 +103,7 @@ class UserEncoder(nn.Module):
         self.drop = nn.Dropout(0.2)
         self.pool_attn = AttentivePooling(dim)
         self.tail = tail
-        self.gru = nn.GRU(dim, dim, batch_first=True)
+        self.gru = FusedGRU(dim, dim)
         self.pool_fuse = AttentivePooling(dim)
 
     def forward(self, news_vecs):             # [B, H, D] -> [B, D]

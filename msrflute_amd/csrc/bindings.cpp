@@ -595,6 +595,84 @@ std::vector<torch::Tensor> gru_seq_bwd(torch::Tensor gates, torch::Tensor ghn,
   return {dgi, dgh};
 }
 
+// fused GRU recurrence for any H % 4 == 0, 4 <= H <= 512 (gru_seq_any.hip):
+// fp32, K-stacked packs, row r -> client r / rows_per_client.  Returns K.
+static long long gru_any_clients(const torch::Tensor& x3h, const char* name,
+                                 const torch::Tensor& w, int64_t groups,
+                                 int64_t cols, const char* layout,
+                                 int64_t rows_per_client) {
+  check_flat(x3h, name); check_flat(w, "the packed W_hh stack");
+  TORCH_CHECK(x3h.dim() == 3 && x3h.size(2) % 3 == 0, name,
+              " must be [R, T, 3H]");
+  long long R = x3h.size(0), H = x3h.size(2) / 3;
+  TORCH_CHECK(H % 4 == 0 && H >= 4 && H <= 512,
+              "the any-H fused GRU supports hidden sizes with H % 4 == 0 and "
+              "4 <= H <= 512, got H = ", H);
+  TORCH_CHECK(rows_per_client > 0 && R % rows_per_client == 0,
+              "R = ", R, " rows must be a multiple of rows_per_client");
+  long long K = R / rows_per_client;
+  TORCH_CHECK(w.dim() == 4 && w.size(0) == K && w.size(1) == groups &&
+              w.size(2) == cols && w.size(3) == 4 &&
+              reinterpret_cast<uintptr_t>(w.data_ptr()) % 16 == 0,
+              "W_hh must be the 16-byte aligned float4 pack ", layout,
+              " with K = ", K, ", H = ", H);
+  return K;
+}
+
+std::vector<torch::Tensor> gru_seq_any_fwd(torch::Tensor gi,
+                                           torch::Tensor whh_t_stack,
+                                           torch::Tensor b_hh_stack,
+                                           int64_t rows_per_client) {
+  long long H = gi.dim() == 3 ? gi.size(2) / 3 : 0;
+  long long K = gru_any_clients(
+      gi, "gi", whh_t_stack, H / 4, 3 * H,
+      "[K, H/4, 3H, 4] (ops/lstm._gru_pack_fwd)", rows_per_client);
+  check_flat(b_hh_stack, "b_hh_stack");
+  TORCH_CHECK(b_hh_stack.numel() == K * 3 * H, "b_hh_stack must be [K, 3H]");
+  long long R = gi.size(0), T = gi.size(1);
+  auto h_seq = torch::empty({R, T, H}, gi.options());
+  auto gates = torch::empty({R, T, 3 * H}, gi.options());
+  auto ghn = torch::empty({R, T, H}, gi.options());
+  if (R > 0 && T > 0)
+    launch_gru_seq_any_fwd(gi.data_ptr<float>(),
+                           whh_t_stack.data_ptr<float>(),
+                           b_hh_stack.data_ptr<float>(),
+                           h_seq.data_ptr<float>(), gates.data_ptr<float>(),
+                           ghn.data_ptr<float>(), (int)R,
+                           (int)rows_per_client, (int)T, (int)H,
+                           cur_stream());
+  return {h_seq, gates, ghn};
+}
+
+std::vector<torch::Tensor> gru_seq_any_bwd(torch::Tensor gates,
+                                           torch::Tensor ghn,
+                                           torch::Tensor h_seq,
+                                           torch::Tensor w_hh_stack,
+                                           torch::Tensor dh_out,
+                                           int64_t rows_per_client) {
+  long long H = gates.dim() == 3 ? gates.size(2) / 3 : 0;
+  gru_any_clients(gates, "gates", w_hh_stack, 3 * H / 4, H,
+                  "[K, 3H/4, H, 4] (ops/lstm._gru_pack_bwd)",
+                  rows_per_client);
+  check_flat(ghn, "ghn"); check_flat(h_seq, "h_seq");
+  check_flat(dh_out, "dh_out");
+  long long R = gates.size(0), T = gates.size(1);
+  TORCH_CHECK(ghn.numel() == R * T * H && h_seq.numel() == R * T * H &&
+              dh_out.numel() == R * T * H,
+              "ghn, h_seq and dh_out must be [R, T, H]");
+  auto dgi = torch::empty_like(gates);
+  auto dgh = torch::empty_like(gates);
+  if (R > 0 && T > 0)
+    launch_gru_seq_any_bwd(gates.data_ptr<float>(), ghn.data_ptr<float>(),
+                           h_seq.data_ptr<float>(),
+                           w_hh_stack.data_ptr<float>(),
+                           dh_out.data_ptr<float>(), dgi.data_ptr<float>(),
+                           dgh.data_ptr<float>(), (int)R,
+                           (int)rows_per_client, (int)T, (int)H,
+                           cur_stream());
+  return {dgi, dgh};
+}
+
 // fused GRU gate math (no-grad eval path of the nlg_gru recurrence)
 torch::Tensor gru_gates(torch::Tensor g_i, torch::Tensor g_h,
                         torch::Tensor h) {
@@ -1128,5 +1206,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("lstm_seq_fwd", &lstm_seq_fwd);
   m.def("gru_seq_fwd", &gru_seq_fwd);
   m.def("gru_seq_bwd", &gru_seq_bwd);
+  m.def("gru_seq_any_fwd", &gru_seq_any_fwd);
+  m.def("gru_seq_any_bwd", &gru_seq_any_bwd);
   m.def("lstm_seq_bwd", &lstm_seq_bwd);
 }

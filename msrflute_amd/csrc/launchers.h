@@ -168,6 +168,20 @@ void launch_gru_seq_bwd_bf16(const float* gates, const float* ghn,
                              const float* h_seq, const unsigned short* w_hh,
                              const float* dh_out, float* dgi, float* dgh,
                              int B, int T, hipStream_t s);
+// gru_seq_any.hip — any H with H % 4 == 0 and 4 <= H <= 512 (checked by
+// the bindings), fp32, K-stacked like the LSTM: whh_t_stack [K, H/4, 3H, 4],
+// w_hh_stack [K, 3H/4, H, 4], b_hh_stack [K, 3H]; row r of the R rows
+// belongs to client r / rows_per_client
+void launch_gru_seq_any_fwd(const float* gi, const float* whh_t_stack,
+                            const float* b_hh_stack, float* h_seq,
+                            float* gates, float* ghn, int R,
+                            int rows_per_client, int T, int H,
+                            hipStream_t s);
+void launch_gru_seq_any_bwd(const float* gates, const float* ghn,
+                            const float* h_seq, const float* w_hh_stack,
+                            const float* dh_out, float* dgi, float* dgh,
+                            int R, int rows_per_client, int T, int H,
+                            hipStream_t s);
 
 // fused_cnn.hip — drivers.  mu > 0 (FedProx) makes the clip/SGD tail of
 // every step use g + mu (w - server) and adds 0.5 mu ||w - server||^2 to

@@ -172,17 +172,19 @@ class FusedLSTM(nn.Module):
 
 
 def _gru_pack_fwd(w_hh):
-    """[3H, H] -> float4-packed [H/4, 3H, 4]: element (kk, j, d) =
-    W_hh[j, 4kk+d] (the LSTM's _pack_fwd with 3H gate columns)."""
-    H3, H = w_hh.shape
-    return w_hh.t().reshape(H // 4, 4, H3).permute(0, 2, 1).contiguous()
+    """[..., 3H, H] -> float4-packed [..., H/4, 3H, 4]: element (kk, j, d) =
+    W_hh[j, 4kk+d] (the LSTM's _pack_fwd with 3H gate columns).  Leading
+    dims (the client stack of the any-H pair) pass through."""
+    *lead, H3, H = w_hh.shape
+    return w_hh.transpose(-1, -2).reshape(*lead, H // 4, 4, H3) \
+        .transpose(-1, -2).contiguous()
 
 
 def _gru_pack_bwd(w_hh):
-    """[3H, H] -> float4-packed [3H/4, H, 4]: element (jg, h, d) =
+    """[..., 3H, H] -> float4-packed [..., 3H/4, H, 4]: element (jg, h, d) =
     W_hh[4jg+d, h]."""
-    H3, H = w_hh.shape
-    return w_hh.reshape(H3 // 4, 4, H).permute(0, 2, 1).contiguous()
+    *lead, H3, H = w_hh.shape
+    return w_hh.reshape(*lead, H3 // 4, 4, H).transpose(-1, -2).contiguous()
 
 
 def _gru_pack_fwd_bf16(w_hh):
@@ -208,20 +210,30 @@ def _gru_packs(bf16_weights):
 
 
 class _GRUSeq(torch.autograd.Function):
-    """Fused GRU sequence (csrc/gru_seq.hip) — reference cell semantics
-    (experiments/nlg_gru/model.py GRU2).
+    """Fused GRU sequence — reference cell semantics
+    (experiments/nlg_gru/model.py GRU2, which are ``nn.GRU``'s).  The
+    kernel pair is picked from H: 512 runs ``k_gru_seq_fwd/_bwd``
+    (csrc/gru_seq.hip), any other H with H % 4 == 0 and 4 <= H <= 512 runs
+    ``k_gru_seq_any_fwd/_bwd`` (csrc/gru_seq_any.hip) at K = 1.
 
-    ``bf16_weights``: both kernels read W_hh rounded to bf16 (packed anew
-    on every call — SGD moves the fp32 masters every step) and compute in
-    fp32, i.e. the recurrence evaluated at ``w_hh.bfloat16().float()``;
-    dW_hh and db_hh are the same fp32 GEMM and sum over the kernel's dgh
-    and land on the masters (straight-through)."""
+    ``bf16_weights`` (H = 512 only; the any-H pair has no bf16 form, so the
+    flag is ignored at other sizes and the fp32 pair runs): both kernels
+    read W_hh rounded to bf16 (packed anew on every call — SGD moves the
+    fp32 masters every step) and compute in fp32, i.e. the recurrence
+    evaluated at ``w_hh.bfloat16().float()``; dW_hh and db_hh are the same
+    fp32 GEMM and sum over the kernel's dgh and land on the masters
+    (straight-through)."""
 
     @staticmethod
     def forward(ctx, gi, w_hh, b_hh, bf16_weights=False):
-        pack = _gru_packs(bf16_weights)[0]
-        h_seq, gates, ghn = _C.gru_seq_fwd(
-            gi.contiguous(), pack(w_hh), b_hh.contiguous())
+        if w_hh.shape[-1] == 512:
+            pack = _gru_packs(bf16_weights)[0]
+            h_seq, gates, ghn = _C.gru_seq_fwd(
+                gi.contiguous(), pack(w_hh), b_hh.contiguous())
+        else:
+            h_seq, gates, ghn = _C.gru_seq_any_fwd(
+                gi.contiguous(), _gru_pack_fwd(w_hh.unsqueeze(0)),
+                b_hh.contiguous(), gi.shape[0])
         ctx.save_for_backward(gates, ghn, h_seq, w_hh)
         ctx.bf16_weights = bf16_weights
         return h_seq
@@ -229,10 +241,15 @@ class _GRUSeq(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dh):
         gates, ghn, h_seq, w_hh = ctx.saved_tensors
-        pack = _gru_packs(ctx.bf16_weights)[1]
-        dgi, dgh = _C.gru_seq_bwd(gates, ghn, h_seq, pack(w_hh),
-                                  dh.contiguous())
         B, T, H = h_seq.shape
+        if H == 512:
+            pack = _gru_packs(ctx.bf16_weights)[1]
+            dgi, dgh = _C.gru_seq_bwd(gates, ghn, h_seq, pack(w_hh),
+                                      dh.contiguous())
+        else:
+            dgi, dgh = _C.gru_seq_any_bwd(
+                gates, ghn, h_seq, _gru_pack_bwd(w_hh.unsqueeze(0)),
+                dh.contiguous(), B)
         h_prev = torch.cat([h_seq.new_zeros(B, 1, H), h_seq[:, :-1]], dim=1)
         dw_hh = dgh.reshape(-1, 3 * H).t().mm(h_prev.reshape(-1, H))
         db_hh = dgh.sum(dim=(0, 1))
@@ -240,9 +257,53 @@ class _GRUSeq(torch.autograd.Function):
 
 
 def fused_gru_available(hidden_size, x):
-    return HAS_EXT and x.is_cuda and hidden_size == 512 \
-        and x.dtype == torch.float32
+    """True when ``fused_gru_seq`` serves this hidden size and input:
+    H % 4 == 0, 4 <= H <= 512, float32 on the GPU, extension built."""
+    return HAS_EXT and x.is_cuda and hidden_size % 4 == 0 \
+        and 4 <= hidden_size <= 512 and x.dtype == torch.float32
 
 
 def fused_gru_seq(gi, w_hh_weight, w_hh_bias, bf16_weights=False):
+    """``bf16_weights`` applies at H = 512 only (see ``_GRUSeq``)."""
     return _GRUSeq.apply(gi, w_hh_weight, w_hh_bias, bool(bf16_weights))
+
+
+class FusedGRU(nn.Module):
+    """Unidirectional batch-first GRU, drop-in for ``nn.GRU`` (no dropout,
+    biases on).  Hidden sizes with H % 4 == 0 and 4 <= H <= 512 run the
+    fused recurrence on the GPU in float32: per layer one GEMM
+    ``gi = x @ W_ih^T + b_ih`` for all steps, then ``_GRUSeq``.  Always
+    fp32: there is no ``bf16_recurrent`` here, the any-H pair has no bf16
+    form.  On the CPU, for other dtypes or sizes, and whenever ``hx`` is
+    given, an unregistered ``nn.GRU`` sharing the SAME Parameter objects
+    (``weight_ih_l{k}`` …, so checkpoints interchange) runs instead.
+    Returns ``(h_seq, h_n)`` with ``h_n`` of shape [num_layers, B, H]."""
+
+    def __init__(self, input_size, hidden_size, num_layers=1,
+                 batch_first=True):
+        super().__init__()
+        assert batch_first
+        self.input_size = input_size
+        self.hidden_size = hidden_size
+        self.num_layers = num_layers
+        fallback = nn.GRU(input_size, hidden_size, num_layers=num_layers,
+                          batch_first=True)
+        # as in FusedLSTM: the fallback's Parameters under nn.GRU's names,
+        # the fallback itself unregistered so state_dict stays clean
+        for name, p in list(fallback.named_parameters()):
+            self.register_parameter(name, p)
+        object.__setattr__(self, "_fallback", fallback)
+
+    def forward(self, x, hx=None):
+        if hx is not None or x.dim() != 3 or x.shape[1] == 0 \
+                or not fused_gru_available(self.hidden_size, x):
+            self._fallback.flatten_parameters = lambda: None  # shared params
+            return self._fallback(x, hx)
+        h, last = x, []
+        for k in range(self.num_layers):
+            gi = h.matmul(getattr(self, f"weight_ih_l{k}").t()) \
+                + getattr(self, f"bias_ih_l{k}")
+            h = _GRUSeq.apply(gi, getattr(self, f"weight_hh_l{k}"),
+                              getattr(self, f"bias_hh_l{k}"))
+            last.append(h[:, -1])
+        return h, torch.stack(last, dim=0)
