@@ -6,8 +6,13 @@ pooling, UserEncoder attention + GRU-tail fusion, frozen pretrained
 embeddings) and model.py:47-129 (AUC/MRR/nDCG metrics).
 
 MI355X-native divergences: multi-head attention uses
-``F.scaled_dot_product_attention`` (fused flash-style kernel on ROCm)
-instead of 4 einsum kernels; the embedding matrix is random-init frozen
+``F.scaled_dot_product_attention`` instead of 4 einsum kernels;
+``model_config.fused_attention: true`` runs it as ``fused_mha``
+(csrc/mha_small.hip: one launch forward and one backward on the projection
+GEMMs' own [B, L, heads*d] layout; L <= 64, d <= 32, float32 on the GPU).
+It is off by default: measured at the task's shapes it is not faster than
+SDPA (PERF.md, "Short-sequence attention").  The embedding matrix is
+random-init frozen
 (no GloVe download offline — pass ``embedding_path`` to a local ``.npy``
 to load real vectors); metrics are computed in torch (no sklearn/nltk);
 the user encoder's GRU over the last 20 clicks is ``FusedGRU`` (H = 400:
@@ -26,6 +31,7 @@ from torch import nn
 from torch.nn import functional as F
 
 from msrflute_amd.core.model import BaseModel
+from msrflute_amd.ops.attention import fused_mha, fused_mha_available
 from msrflute_amd.ops.lstm import FusedGRU
 from msrflute_amd.utils import to_device
 
@@ -51,10 +57,13 @@ class AttentivePooling(nn.Module):
 
 class SelfAttention(nn.Module):
     """Multi-head self-attention via SDPA (reference Attention module,
-    fednewsrec_model.py:44-106, was einsum-based)."""
+    fednewsrec_model.py:44-106, was einsum-based).  With ``fused`` set it is
+    ``fused_mha`` on the three projections where ``fused_mha_available``
+    says so, and SDPA on head views otherwise."""
 
-    def __init__(self, dim, heads, head_dim):
+    def __init__(self, dim, heads, head_dim, fused=False):
         super().__init__()
+        self.fused = fused
         self.heads, self.head_dim = heads, head_dim
         out = heads * head_dim
         self.wq = nn.Linear(dim, out, bias=False)
@@ -65,6 +74,8 @@ class SelfAttention(nn.Module):
 
     def forward(self, x):                     # [B, L, D] -> [B, L, H*Hd]
         B, L, _ = x.shape
+        if self.fused and fused_mha_available(L, self.head_dim, x):
+            return fused_mha(self.wq(x), self.wk(x), self.wv(x), self.heads)
         q = self.wq(x).view(B, L, self.heads, self.head_dim).transpose(1, 2)
         k = self.wk(x).view(B, L, self.heads, self.head_dim).transpose(1, 2)
         v = self.wv(x).view(B, L, self.heads, self.head_dim).transpose(1, 2)
@@ -180,6 +191,9 @@ class FEDNEWS(BaseModel):
             matrix[0] = 0.0
         self.net = FedNewsRecNet(matrix, freeze_embeddings=bool(
             model_config.get("freeze_embeddings", True)))
+        for m in self.net.modules():
+            if isinstance(m, SelfAttention):
+                m.fused = bool(model_config.get("fused_attention", False))
 
     def loss(self, input):
         if not self.net.training:

@@ -673,6 +673,88 @@ std::vector<torch::Tensor> gru_seq_any_bwd(torch::Tensor gates,
   return {dgi, dgh};
 }
 
+// fused attention for short sequences (mha_small.hip): fp32, 1 <= L <= 64,
+// d % 4 == 0, 4 <= d <= 32, scale 1/sqrt(d).  q, k, v are [N, L, E] views
+// with unit element stride and one common row stride S: contiguous tensors
+// or slices of one [N, L, 3E] buffer.  Returns S.
+static long long mha_row_stride(const torch::Tensor& t, const char* name,
+                                const torch::Tensor& like) {
+  TORCH_CHECK(t.is_cuda(), name, " must be on GPU");
+  TORCH_CHECK(t.scalar_type() == torch::kFloat32, name, " must be fp32");
+  TORCH_CHECK(t.dim() == 3, name, " must be [N, L, heads*d]");
+  TORCH_CHECK(t.sizes() == like.sizes(), name, " must have q's shape");
+  long long N = t.size(0), L = t.size(1), E = t.size(2);
+  long long S = L > 1 ? t.stride(1) : (N > 1 ? t.stride(0) : E);
+  TORCH_CHECK(t.stride(2) == 1 && (L == 1 || t.stride(1) == S) &&
+              (N == 1 || t.stride(0) == L * S) && S >= E,
+              name, " must have unit element stride and rows a constant S "
+              "floats apart (row (n, i) at (n*L + i)*S), got strides ",
+              t.strides());
+  TORCH_CHECK(S % 4 == 0, name, ": row stride S = ", S,
+              " must be a multiple of 4 floats");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0, name,
+              " must be 16-byte aligned");
+  return S;
+}
+
+static long long mha_check(const torch::Tensor& q, const torch::Tensor& k,
+                           const torch::Tensor& v, int64_t heads) {
+  long long S = mha_row_stride(q, "q", q);
+  TORCH_CHECK(mha_row_stride(k, "k", q) == S &&
+              mha_row_stride(v, "v", q) == S,
+              "q, k and v must share one row stride, q has S = ", S);
+  long long L = q.size(1), E = q.size(2);
+  TORCH_CHECK(L >= 1 && L <= 64,
+              "the fused attention supports 1 <= L <= 64, got L = ", L);
+  TORCH_CHECK(heads >= 1 && E % heads == 0, "E = ", E,
+              " must be a multiple of heads = ", heads);
+  long long d = E / heads;
+  TORCH_CHECK(d % 4 == 0 && d >= 4 && d <= 32,
+              "the fused attention supports head dimensions with d % 4 == 0 "
+              "and 4 <= d <= 32, got d = ", d);
+  return S;
+}
+
+std::vector<torch::Tensor> mha_small_fwd(torch::Tensor q, torch::Tensor k,
+                                         torch::Tensor v, int64_t heads) {
+  long long S = mha_check(q, k, v, heads);
+  long long N = q.size(0), L = q.size(1), E = q.size(2);
+  auto o = torch::empty({N, L, E}, q.options());
+  auto lse = torch::empty({N, heads, L}, q.options());
+  if (N > 0)
+    launch_mha_small_fwd(q.data_ptr<float>(), k.data_ptr<float>(),
+                         v.data_ptr<float>(), o.data_ptr<float>(),
+                         lse.data_ptr<float>(), (int)N, (int)L, (int)heads,
+                         (int)(E / heads), S, cur_stream());
+  return {o, lse};
+}
+
+std::vector<torch::Tensor> mha_small_bwd(torch::Tensor q, torch::Tensor k,
+                                         torch::Tensor v, torch::Tensor o,
+                                         torch::Tensor lse,
+                                         torch::Tensor d_o) {
+  check_flat(lse, "lse"); check_flat(o, "o"); check_flat(d_o, "do");
+  TORCH_CHECK(q.dim() == 3 && lse.dim() == 3 && lse.size(0) == q.size(0) &&
+              lse.size(1) >= 1 && lse.size(2) == q.size(1),
+              "lse must be [N, heads, L]");
+  long long heads = lse.size(1);
+  long long S = mha_check(q, k, v, heads);
+  TORCH_CHECK(o.sizes() == q.sizes() && d_o.sizes() == q.sizes(),
+              "o and do must be contiguous [N, L, heads*d]");
+  long long N = q.size(0), L = q.size(1), E = q.size(2);
+  auto dq = torch::empty({N, L, E}, q.options());
+  auto dk = torch::empty({N, L, E}, q.options());
+  auto dv = torch::empty({N, L, E}, q.options());
+  if (N > 0)
+    launch_mha_small_bwd(q.data_ptr<float>(), k.data_ptr<float>(),
+                         v.data_ptr<float>(), o.data_ptr<float>(),
+                         lse.data_ptr<float>(), d_o.data_ptr<float>(),
+                         dq.data_ptr<float>(), dk.data_ptr<float>(),
+                         dv.data_ptr<float>(), (int)N, (int)L, (int)heads,
+                         (int)(E / heads), S, cur_stream());
+  return {dq, dk, dv};
+}
+
 // fused GRU gate math (no-grad eval path of the nlg_gru recurrence)
 torch::Tensor gru_gates(torch::Tensor g_i, torch::Tensor g_h,
                         torch::Tensor h) {
@@ -1208,5 +1290,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gru_seq_bwd", &gru_seq_bwd);
   m.def("gru_seq_any_fwd", &gru_seq_any_fwd);
   m.def("gru_seq_any_bwd", &gru_seq_any_bwd);
+  m.def("mha_small_fwd", &mha_small_fwd);
+  m.def("mha_small_bwd", &mha_small_bwd);
   m.def("lstm_seq_bwd", &lstm_seq_bwd);
 }

@@ -183,6 +183,19 @@ void launch_gru_seq_any_bwd(const float* gates, const float* ghn,
                             int R, int rows_per_client, int T, int H,
                             hipStream_t s);
 
+// mha_small.hip — fused attention for 1 <= L <= 64, d % 4 == 0 and
+// 4 <= d <= 32 (checked by the bindings), fp32, scale 1/sqrt(d).  q, k, v:
+// head hd of row (n, i) at (n*L + i)*S + hd*d floats, S % 4 == 0, bases
+// 16-byte aligned; o, d_o, dq, dk, dv contiguous [N, L, heads*d];
+// lse [N, heads, L]
+void launch_mha_small_fwd(const float* q, const float* k, const float* v,
+                          float* o, float* lse, int N, int L, int heads,
+                          int d, long long S, hipStream_t s);
+void launch_mha_small_bwd(const float* q, const float* k, const float* v,
+                          const float* o, const float* lse, const float* d_o,
+                          float* dq, float* dk, float* dv, int N, int L,
+                          int heads, int d, long long S, hipStream_t s);
+
 // fused_cnn.hip — drivers.  mu > 0 (FedProx) makes the clip/SGD tail of
 // every step use g + mu (w - server) and adds 0.5 mu ||w - server||^2 to
 // the step's loss, for the clients active at that step; mu == 0 launches

@@ -43,9 +43,11 @@ class Build(BuildExtension):
 
     The any-H GRU pair (gru_seq_any.hip) is built the same way: its scalar
     fmaf chains are the design, and the compile figures and times recorded
-    in docs/kernels.md are those of the code without packed pairs."""
+    in docs/kernels.md are those of the code without packed pairs.  So is
+    the short-sequence attention pair (mha_small.hip), for the same reason:
+    four scalar fmaf chains per dot product in a fixed order."""
 
-    NO_PACKED_FP32 = ("gru_seq_bf16", "gru_seq_any")
+    NO_PACKED_FP32 = ("gru_seq_bf16", "gru_seq_any", "mha_small")
 
     def build_extensions(self):
         os.makedirs(self.build_temp, exist_ok=True)
