@@ -11,7 +11,11 @@ MI355X-native divergences: multi-head attention uses
 (csrc/mha_small.hip: one launch forward and one backward on the projection
 GEMMs' own [B, L, heads*d] layout; L <= 64, d <= 32, float32 on the GPU).
 It is off by default: measured at the task's shapes it is not faster than
-SDPA (PERF.md, "Short-sequence attention").  The embedding matrix is
+SDPA (PERF.md, "Short-sequence attention").
+``model_config.fused_pooling: true`` runs the three attentive poolings as
+``fused_attentive_pool`` (csrc/attn_pool.hip: one launch forward and one
+backward on the fp32 MFMA; L <= 64, D <= 512, hidden <= 256, float32 on the
+GPU); off by default (PERF.md, "Attentive pooling").  The embedding matrix is
 random-init frozen
 (no GloVe download offline — pass ``embedding_path`` to a local ``.npy``
 to load real vectors); metrics are computed in torch (no sklearn/nltk);
@@ -31,7 +35,9 @@ from torch import nn
 from torch.nn import functional as F
 
 from msrflute_amd.core.model import BaseModel
-from msrflute_amd.ops.attention import fused_mha, fused_mha_available
+from msrflute_amd.ops.attention import (fused_attentive_pool,
+                                        fused_attentive_pool_available,
+                                        fused_mha, fused_mha_available)
 from msrflute_amd.ops.lstm import FusedGRU
 from msrflute_amd.utils import to_device
 
@@ -40,16 +46,24 @@ NPRATIO = 4
 
 class AttentivePooling(nn.Module):
     """Additive attention pooling over a sequence (reference
-    fednewsrec_model.py:12-42)."""
+    fednewsrec_model.py:12-42).  With ``fused`` set it is
+    ``fused_attentive_pool`` on ``dense`` / ``dense2``'s own parameters where
+    ``fused_attentive_pool_available`` says so; the dropout stays ahead of
+    it."""
 
-    def __init__(self, dim, hidden=200, dropout=0.2):
+    def __init__(self, dim, hidden=200, dropout=0.2, fused=False):
         super().__init__()
+        self.fused = fused
         self.drop = nn.Dropout(dropout)
         self.dense = nn.Linear(dim, hidden)
         self.dense2 = nn.Linear(hidden, 1)
 
     def forward(self, x):                     # [B, L, D] -> [B, D]
         x = self.drop(x)
+        if self.fused and fused_attentive_pool_available(
+                x.shape[1], x.shape[2], self.dense.out_features, x):
+            return fused_attentive_pool(x, self.dense.weight, self.dense.bias,
+                                        self.dense2.weight, self.dense2.bias)
         att = self.dense2(torch.tanh(self.dense(x))).squeeze(-1)
         att = torch.softmax(att, dim=1)
         return torch.einsum("bld,bl->bd", x, att)
@@ -194,6 +208,8 @@ class FEDNEWS(BaseModel):
         for m in self.net.modules():
             if isinstance(m, SelfAttention):
                 m.fused = bool(model_config.get("fused_attention", False))
+            if isinstance(m, AttentivePooling):
+                m.fused = bool(model_config.get("fused_pooling", False))
 
     def loss(self, input):
         if not self.net.training:

@@ -755,6 +755,80 @@ std::vector<torch::Tensor> mha_small_bwd(torch::Tensor q, torch::Tensor k,
   return {dq, dk, dv};
 }
 
+// fused attentive pooling (attn_pool.hip): fp32, 1 <= L <= 64, D % 4 == 0
+// with 4 <= D <= 512, Hd % 4 == 0 with 4 <= Hd <= 256.  w1 is dense.weight
+// [Hd, D] as it is (no packed layout), w2 is dense2.weight as [Hd].
+static void pool_tensor(const torch::Tensor& t, const char* name,
+                        at::IntArrayRef shape, const char* layout) {
+  check_flat(t, name);
+  TORCH_CHECK(t.sizes() == shape, name, " must be ", layout, " = ", shape,
+              ", got ", t.sizes());
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0, name,
+              " must be 16-byte aligned");
+}
+
+static void pool_check(const torch::Tensor& x, const torch::Tensor& w1,
+                       const torch::Tensor& w2) {
+  check_flat(x, "x");
+  TORCH_CHECK(x.dim() == 3, "x must be [N, L, D]");
+  TORCH_CHECK(w1.dim() == 2, "w1 must be [Hd, D]");
+  long long L = x.size(1), D = x.size(2), Hd = w1.size(0);
+  TORCH_CHECK(L >= 1 && L <= 64,
+              "the fused attentive pooling supports 1 <= L <= 64, got L = ",
+              L);
+  TORCH_CHECK(D % 4 == 0 && D >= 4 && D <= 512,
+              "the fused attentive pooling supports D % 4 == 0 and "
+              "4 <= D <= 512, got D = ", D);
+  TORCH_CHECK(Hd % 4 == 0 && Hd >= 4 && Hd <= 256,
+              "the fused attentive pooling supports Hd % 4 == 0 and "
+              "4 <= Hd <= 256, got Hd = ", Hd);
+  pool_tensor(x, "x", x.sizes(), "[N, L, D]");
+  pool_tensor(w1, "w1", {Hd, D}, "[Hd, D] row-major");
+  pool_tensor(w2, "w2", {Hd}, "[Hd]");
+}
+
+std::vector<torch::Tensor> attn_pool_fwd(torch::Tensor x, torch::Tensor w1,
+                                         torch::Tensor b1, torch::Tensor w2,
+                                         torch::Tensor b2, bool save_e) {
+  pool_check(x, w1, w2);
+  long long N = x.size(0), L = x.size(1), D = x.size(2), Hd = w1.size(0);
+  pool_tensor(b1, "b1", {Hd}, "[Hd]");
+  pool_tensor(b2, "b2", {1}, "[1]");
+  auto y = torch::empty({N, D}, x.options());
+  auto p = torch::empty({N, L}, x.options());
+  auto e = torch::empty({save_e ? N : 0, L, Hd}, x.options());
+  if (N > 0)
+    launch_attn_pool_fwd(x.data_ptr<float>(), w1.data_ptr<float>(),
+                         b1.data_ptr<float>(), w2.data_ptr<float>(),
+                         b2.data_ptr<float>(), y.data_ptr<float>(),
+                         p.data_ptr<float>(),
+                         save_e ? e.data_ptr<float>() : nullptr, (int)N,
+                         (int)L, (int)D, (int)Hd, save_e ? 1 : 0,
+                         cur_stream());
+  return {y, p, e};
+}
+
+std::vector<torch::Tensor> attn_pool_bwd(torch::Tensor x, torch::Tensor e,
+                                         torch::Tensor p, torch::Tensor w1,
+                                         torch::Tensor w2, torch::Tensor dy) {
+  pool_check(x, w1, w2);
+  long long N = x.size(0), L = x.size(1), D = x.size(2), Hd = w1.size(0);
+  pool_tensor(e, "e", {N, L, Hd}, "[N, L, Hd]");
+  pool_tensor(p, "p", {N, L}, "[N, L]");
+  pool_tensor(dy, "dy", {N, D}, "[N, D]");
+  auto dx = torch::empty({N, L, D}, x.options());
+  auto dz = torch::empty({N, L, Hd}, x.options());
+  auto da = torch::empty({N, L}, x.options());
+  if (N > 0)
+    launch_attn_pool_bwd(x.data_ptr<float>(), e.data_ptr<float>(),
+                         p.data_ptr<float>(), w1.data_ptr<float>(),
+                         w2.data_ptr<float>(), dy.data_ptr<float>(),
+                         dx.data_ptr<float>(), dz.data_ptr<float>(),
+                         da.data_ptr<float>(), (int)N, (int)L, (int)D,
+                         (int)Hd, cur_stream());
+  return {dx, dz, da};
+}
+
 // fused GRU gate math (no-grad eval path of the nlg_gru recurrence)
 torch::Tensor gru_gates(torch::Tensor g_i, torch::Tensor g_h,
                         torch::Tensor h) {
@@ -1292,5 +1366,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gru_seq_any_bwd", &gru_seq_any_bwd);
   m.def("mha_small_fwd", &mha_small_fwd);
   m.def("mha_small_bwd", &mha_small_bwd);
+  m.def("attn_pool_fwd", &attn_pool_fwd);
+  m.def("attn_pool_bwd", &attn_pool_bwd);
   m.def("lstm_seq_bwd", &lstm_seq_bwd);
 }

@@ -196,6 +196,20 @@ void launch_mha_small_bwd(const float* q, const float* k, const float* v,
                           float* dq, float* dk, float* dv, int N, int L,
                           int heads, int d, long long S, hipStream_t s);
 
+// attn_pool.hip — fused attentive pooling for 1 <= L <= 64, D % 4 == 0 with
+// 4 <= D <= 512, Hd % 4 == 0 with 4 <= Hd <= 256 (checked by the bindings),
+// fp32, everything contiguous and 16-byte aligned: x, dx [N, L, D];
+// w1 [Hd, D]; b1, w2 [Hd]; b2 [1]; y, dy [N, D]; p, da [N, L];
+// e, dz [N, L, Hd].  e is not written (and may be null) when save_e == 0.
+void launch_attn_pool_fwd(const float* x, const float* w1, const float* b1,
+                          const float* w2, const float* b2, float* y,
+                          float* p, float* e, int N, int L, int D, int Hd,
+                          int save_e, hipStream_t s);
+void launch_attn_pool_bwd(const float* x, const float* e, const float* p,
+                          const float* w1, const float* w2, const float* dy,
+                          float* dx, float* dz, float* da, int N, int L,
+                          int D, int Hd, hipStream_t s);
+
 // fused_cnn.hip — drivers.  mu > 0 (FedProx) makes the clip/SGD tail of
 // every step use g + mu (w - server) and adds 0.5 mu ||w - server||^2 to
 // the step's loss, for the clients active at that step; mu == 0 launches

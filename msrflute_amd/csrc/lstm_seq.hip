@@ -37,6 +37,7 @@
 #include <hip/hip_runtime.h>
 
 #include "launchers.h"
+#include "scalar_math.h"
 
 #define LSTM_H 256           // hidden size of the benchmark model
 // float4 weight groups each thread keeps in registers across all T steps
@@ -307,55 +308,13 @@ void k_lstm_seq_bwd(const float* __restrict__ gates,
 // carries the attribute only so that tanh_s is the same code, bit for
 // bit, in the kernel that saves the states and the one that reads them.
 // A function with its own target features cannot inline the device
-// library or the HIP headers, so the two transcendentals, the quad
-// exchange and the barrier are written here on builtins, always inlined.
-#if defined(__HIP_DEVICE_COMPILE__)
-#define LSTM_SCALAR_F32 __attribute__((target("no-packed-fp32-ops")))
-#else
-#define LSTM_SCALAR_F32
-#endif
-#define LSTM_INL __device__ __forceinline__ LSTM_SCALAR_F32
-
-// e^x for |x| <= 87 (clamped: every result stays a finite normal):
-// v_exp_f32 (1 ulp) on x * log2(e), with the rounding error of that
-// product, which |x| would amplify, put back to first order.  The clamp
-// is two compare-and-selects, not fmin / fmax: v_min_f32 / v_max_f32
-// return the operand that is not a NaN, and a NaN pre-activation (a
-// client that diverged upstream) has to come out of sig_s and tanh_s as
-// NaN, as it does out of nn.LSTM and the H = 256 kernels.
-LSTM_INL float exp_s(float x) {
-  x = x < -87.f ? -87.f : x;
-  x = x > 87.f ? 87.f : x;
-  const float l2e_hi = 1.44269502e+0f, l2e_lo = 1.92596299e-8f;
-  float t = x * l2e_hi;
-  float r = __builtin_fmaf(x, l2e_lo, __builtin_fmaf(x, l2e_hi, -t));
-  float e = __builtin_amdgcn_exp2f(t);
-  return __builtin_fmaf(e, r * 0.693147181f, e);
-}
+// library or the HIP headers, so the two transcendentals (scalar_math.h),
+// the quad exchange and the barrier are written on builtins, always
+// inlined.
+#define LSTM_SCALAR_F32 SCALAR_F32
+#define LSTM_INL SCALAR_INL
 
 LSTM_INL float sig_s(float x) { return 1.f / (1.f + exp_s(-x)); }
-
-// tanh: below 0.625 an odd polynomial x + x^3 p(x^2); above it
-// 1 - 2/(e^2x + 1), where the subtraction no longer cancels (it
-// saturates to 1 through the clamp of exp_s).  p is the degree-4
-// least-squares fit of (tanh(x)/x - 1)/x^2 in t = x^2 at 400 Chebyshev
-// nodes of [0, 0.625^2], computed in float64 (numpy
-// Chebyshev.fit -> power basis) and rounded to float32; evaluated as
-// below in float32 its largest relative error over the interval is
-// 1.42 * 2^-24.  tests/test_lstm_small_gpu.py walks the gate inputs
-// across the branch point and into saturation against float64.
-LSTM_INL float tanh_s(float y) {
-  float x = __builtin_fabsf(y);
-  float t = x * x;
-  float p = -0x1.9017fep-8f;
-  p = __builtin_fmaf(p, t, 0x1.581fa6p-6f);
-  p = __builtin_fmaf(p, t, -0x1.b928e0p-5f);
-  p = __builtin_fmaf(p, t, 0x1.110e2ep-3f);
-  p = __builtin_fmaf(p, t, -0x1.555552p-2f);
-  float small = __builtin_fmaf(t, x * p, x);
-  float big = 1.f - 2.f / (exp_s(2.f * x) + 1.f);
-  return __builtin_copysignf(x < 0.625f ? small : big, y);
-}
 
 // lane L of the caller's quad (DPP quad_perm [L, L, L, L]), and the lane
 // at distance 1 / 2 inside it ([1, 0, 3, 2] / [2, 3, 0, 1]); every lane of

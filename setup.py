@@ -45,9 +45,14 @@ class Build(BuildExtension):
     fmaf chains are the design, and the compile figures and times recorded
     in docs/kernels.md are those of the code without packed pairs.  So is
     the short-sequence attention pair (mha_small.hip), for the same reason:
-    four scalar fmaf chains per dot product in a fixed order."""
+    four scalar fmaf chains per dot product in a fixed order.  The
+    attentive pooling pair (attn_pool.hip) joins them: its matrix work is
+    on the MFMA pipe, what is left are scalar fmaf chains in a fixed order,
+    and its tanh / exp (scalar_math.h) are the code the LSTM kernels
+    compile without packed pairs."""
 
-    NO_PACKED_FP32 = ("gru_seq_bf16", "gru_seq_any", "mha_small")
+    NO_PACKED_FP32 = ("gru_seq_bf16", "gru_seq_any", "mha_small",
+                      "attn_pool")
 
     def build_extensions(self):
         os.makedirs(self.build_temp, exist_ok=True)
