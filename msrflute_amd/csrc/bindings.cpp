@@ -8,6 +8,8 @@
 #include <c10/hip/HIPStream.h>
 #include <hip/hip_runtime.h>
 
+#include <climits>
+
 #include "launchers.h"
 
 namespace {
@@ -1028,17 +1030,20 @@ torch::Tensor dbg_conv2_bwd_x_mfma(torch::Tensor dz2, torch::Tensor w2,
 
 std::vector<torch::Tensor> dbg_conv2_bwd_w_mfma(torch::Tensor dz2,
                                                 torch::Tensor a1, int64_t B,
-                                                int64_t K) {
+                                                int64_t K,
+                                                int64_t max_blocks) {
   check_flat(dz2, "dz2"); check_flat(a1, "a1");
   int bs = rows_per_client(B, K);
   TORCH_CHECK(dz2.numel() >= B * 36864 && a1.numel() >= B * 21632);
+  // caps the grid of the tile loop; 0: sized from occupancy
+  TORCH_CHECK(max_blocks >= 0 && max_blocks <= INT_MAX, "max_blocks");
   auto slab = torch::empty({B * 18432}, dz2.options());
   auto dw2 = torch::empty({K * 18432}, dz2.options());
   auto db2 = torch::empty({K * 64}, dz2.options());
   launch_conv2_bwd_w_mfma(dz2.data_ptr<float>(), a1.data_ptr<float>(),
                           bs, (int)K, slab.data_ptr<float>(),
                           dw2.data_ptr<float>(), db2.data_ptr<float>(),
-                          cur_stream());
+                          (int)max_blocks, cur_stream());
   return {dw2, db2};
 }
 
@@ -1330,7 +1335,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("dbg_pool_drop_bwd_bias", &dbg_pool_drop_bwd_bias);
   m.def("dbg_conv2_bwd_x_mfma", &dbg_conv2_bwd_x_mfma);
   m.def("dbg_conv2_bwd_w_mfma", &dbg_conv2_bwd_w_mfma,
-        py::arg("dz2"), py::arg("a1"), py::arg("B"), py::arg("K") = 1);
+        py::arg("dz2"), py::arg("a1"), py::arg("B"), py::arg("K") = 1,
+        py::arg("max_blocks") = 0);
   m.def("dbg_fc1_fwd_mfma", &dbg_fc1_fwd_mfma);
   m.def("dbg_fc1_bwd_w_mfma", &dbg_fc1_bwd_w_mfma,
         py::arg("dz3"), py::arg("a2"), py::arg("B"), py::arg("K") = 1);

@@ -1036,124 +1036,174 @@ void k_pool_drop_bwd_bias_mb(const float* __restrict__ da2,
   conv2_bias_block_sum(s, grads + (long long)k * P + ob2 + co);
 }
 
+// The fp32 conv2 backward-weights kernel walks its tiles with blocks
+// blockIdx.x, blockIdx.x + gridDim.x, ..; the launcher sizes the grid as
+// min(tiles, blocks the device keeps resident), the latter from the
+// runtime's occupancy answer for the kernel as compiled.  Tile -> (image,
+// sub-tile) is a pure function of the tile index and no block waits for
+// another, so the result does not depend on the grid.
+static int conv2_grid(const void* kern, int block, long long tiles,
+                      int max_blocks, int* resident) {
+  if (*resident == 0) {
+    int dev = 0, per_cu = 0, cus = 0;
+    if (hipGetDevice(&dev) != hipSuccess ||
+        hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, block,
+                                                     0) != hipSuccess ||
+        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount,
+                              dev) != hipSuccess ||
+        per_cu < 1 || cus < 1) {
+      fprintf(stderr, "conv2_grid: occupancy query failed\n");
+      abort();
+    }
+    *resident = per_cu * cus;
+  }
+  long long n = tiles < *resident ? tiles : *resident;
+  if (max_blocks > 0 && n > max_blocks) n = max_blocks;
+  return (int)(n < 1 ? 1 : n);
+}
+
+// Walk index v -> tile.  The hardware deals consecutive blocks to the 8
+// XCDs in turn, each with an L2 of its own, and the 9 tiles of an image
+// all read that image's dz2: XCD v % 8 gets a contiguous run of tiles, so
+// an image's dz2 is fetched into one L2, not into eight.  A permutation
+// of the tiles; what a tile computes does not depend on it.
+__device__ __forceinline__ int conv2_xcd_tile(int v, int tiles) {
+  int per = tiles / 8;
+  return v < per * 8 ? (v % 8) * per + v / 8 : v;
+}
+
 // conv2 backward weights (f32 MFMA): per image, dw[co][n] = sum over the
 // 576 output positions o of dz2[co][o] * a1[ci(n)][(y+kh)*26 + x+kw].
-// grid = G * 9, 128 threads; a block owns all 64 co x 32 n columns and
-// walks o in chunks of C2W_ROWS output rows.  Per chunk it stages the
-// dz2 rows in their native [co][o] layout (8 lanes x float4 = one 128 B
-// line per row piece) and the raw rows+2 a1 rows of the <= 5 ci planes
-// its 32 columns touch; no im2col tile and no transposed copy of dz2.
+// 9 tiles per image, 128 threads; a tile is all 64 co x 32 n columns and
+// is walked over o in chunks of C2W_ROWS output rows.  Per chunk the block
+// stages the dz2 rows in their native [co][o] layout (float4 loads, 192 B
+// per co) and the raw rows+2 a1 rows of the <= 5 ci planes its 32 columns
+// touch; no im2col tile and no transposed copy of dz2.  Two rows per chunk
+// keep the block at 14.9 KB of LDS, so 8 blocks fit a CU and the 1800
+// tiles of the benchmark shape (K = 10, bs = 20) are resident at once on
+// 256 CUs; with four rows (28.2 KB, 5 per CU) they took two rounds.
 // The B address is o + 2*(o/24) plus a per-lane (ci,kh,kw) constant: the
 // k-loop is unrolled by one 24-wide output row, so every offset is an
 // immediate.  Wave w owns a 2 x 2 block of accumulators (co 32w..32w+31),
 // each dz2 / a1 fragment feeds 2 MFMAs.  Each image's partial runs over o
 // ascending from 0; k_conv2_bwd_w_fold_mb then sums rows b ascending.
-#define C2W_ROWS 4                      /* output rows per staged chunk */
+#define C2W_ROWS 2                      /* output rows per staged chunk */
+#define C2W_NCH (24 / C2W_ROWS)         /* chunks per tile */
 #define C2W_OC (C2W_ROWS * 24)          /* k (= o) values per chunk */
-#define C2W_LD (C2W_OC + 2)             /* 98 %% 32 = 2: the 16 co x 2 kc of
+#define C2W_LD (C2W_OC + 2)             /* LD / 2 odd: the 16 co x 2 kc of
                                            a 32-lane group hit 32 banks */
 #define C2W_PS ((C2W_ROWS + 2) * 26)    /* staged floats per a1 plane */
-static_assert(24 % C2W_ROWS == 0 && C2W_OC % 32 == 0 && C2W_PS <= 256,
-              "conv2 bwd_w chunk: whole rows, whole 128 B row pieces, an a1 "
-              "plane in two passes of the 128 threads");
+static_assert(24 % C2W_ROWS == 0 && C2W_OC % 16 == 0 && C2W_PS <= 128,
+              "conv2 bwd_w chunk: whole rows; 4 threads x float4 pieces per "
+              "dz2 row, 32 rows a pass; an a1 plane in one pass");
+static_assert(C2W_LD % 2 == 0 && (C2W_LD / 2) % 2 == 1,
+              "conv2 bwd_w: conflict-free dz2 fragment reads");
+static_assert((64 * C2W_LD + 5 * C2W_PS) * 4 * 8 <= 160 * 1024,
+              "conv2 bwd_w: 8 blocks per CU by LDS");
 __global__ __launch_bounds__(128)
+__attribute__((amdgpu_waves_per_eu(4, 4)))  // 8 blocks x 2 waves per CU
 void k_conv2_bwd_w_mfma_mb(const float* __restrict__ dz2,
                            const float* __restrict__ a1, int bs, int K,
                            float* __restrict__ slab) {
   __shared__ __attribute__((aligned(16))) float dzl[64 * C2W_LD];
   __shared__ float apl[5 * C2W_PS];
-  int nb = blockIdx.x % 9;
-  long long g = blockIdx.x / 9;
-  const float* dzb = dz2 + g * 36864;
-  const float* a1b = a1 + g * 21632;
+  int tiles = 9 * K * bs;
   int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   int il = lane & 15, kc = lane >> 4;
-  int ci0 = nb * 32 / 9;
-  int npl = 32 - ci0 < 5 ? 32 - ci0 : 5;
-  int aoff[2], boff[2];
+  int aoff[2];
   #pragma unroll
-  for (int q = 0; q < 2; ++q) {
-    aoff[q] = (w * 32 + q * 16 + il) * C2W_LD + kc;
-    int n = nb * 32 + q * 16 + il;
-    int ci = n / 9, rem = n % 9;
-    boff[q] = (ci - ci0) * C2W_PS + (rem / 3) * 26 + rem % 3 + kc;
-  }
-  f32x4 acc[2][2];
-  acc[0][0] = acc[0][1] = acc[1][0] = acc[1][1] = f32x4{0, 0, 0, 0};
-  int sub = threadIdx.x & 7, r0 = threadIdx.x >> 3;
-  // The next chunk's global loads are issued before the current chunk's
-  // MFMAs and held in registers, so their latency hides behind the
-  // matrix work; only the register -> LDS copy sits between barriers.
-  float4 pdz[4][C2W_OC / 32];
-  float pa[5][2];
-  auto fetch = [&](int c) {
+  for (int q = 0; q < 2; ++q) aoff[q] = (w * 32 + q * 16 + il) * C2W_LD + kc;
+  // The next chunk's global loads (the next tile's first chunk after a
+  // tile's last) are issued before the current chunk's MFMAs and held in
+  // registers, so their latency hides behind the matrix work; only the
+  // register -> LDS copy sits between barriers.
+  int sub = threadIdx.x & 3, r0 = threadIdx.x >> 2;
+  float4 pdz[2][C2W_OC / 16];
+  float pa[5];
+  auto fetch = [&](int v, int c) {
+    int t = conv2_xcd_tile(v, tiles);
+    int nb = t % 9;
+    long long g = t / 9;
+    const float* dzb = dz2 + g * 36864 + c * C2W_OC;
     #pragma unroll
-    for (int it = 0; it < 4; ++it) {
-      const float4* sp = reinterpret_cast<const float4*>(
-          dzb + (r0 + 16 * it) * 576 + c * C2W_OC);
+    for (int it = 0; it < 2; ++it)
       #pragma unroll
-      for (int u = 0; u < C2W_OC / 32; ++u) pdz[it][u] = sp[sub + 8 * u];
-    }
-    #pragma unroll
-    for (int p = 0; p < 5; ++p) {
-      const float* sp = a1b + (ci0 + p) * 676 + c * (C2W_ROWS * 26);
-      #pragma unroll
-      for (int h = 0; h < 2; ++h) {
-        int j = threadIdx.x + 128 * h;
-        pa[p][h] = (p < npl && j < C2W_PS) ? sp[j] : 0.f;
-      }
-    }
-  };
-  fetch(0);
-  for (int c = 0; c < 24 / C2W_ROWS; ++c) {
-    __syncthreads();
-    #pragma unroll
-    for (int it = 0; it < 4; ++it) {
-      float* dp = dzl + (r0 + 16 * it) * C2W_LD;
-      #pragma unroll
-      for (int u = 0; u < C2W_OC / 32; ++u) {
-        float4 v = pdz[it][u];
-        float2* d2 = reinterpret_cast<float2*>(dp + 4 * (sub + 8 * u));
-        d2[0] = float2{v.x, v.y};
-        d2[1] = float2{v.z, v.w};
-      }
-    }
+      for (int u = 0; u < C2W_OC / 16; ++u)
+        pdz[it][u] = *reinterpret_cast<const float4*>(
+            dzb + (r0 + 32 * it) * 576 + 4 * (sub + 4 * u));
+    int ci0 = nb * 32 / 9;
+    int npl = 32 - ci0 < 5 ? 32 - ci0 : 5;
+    const float* a1b = a1 + g * 21632 + ci0 * 676 + c * (C2W_ROWS * 26);
     #pragma unroll
     for (int p = 0; p < 5; ++p)
-      #pragma unroll
-      for (int h = 0; h < 2; ++h) {
-        int j = threadIdx.x + 128 * h;
-        if (j < C2W_PS) apl[p * C2W_PS + j] = pa[p][h];
-      }
-    __syncthreads();
-    if (c + 1 < 24 / C2W_ROWS) fetch(c + 1);
+      pa[p] = (p < npl && threadIdx.x < C2W_PS) ? a1b[p * 676 + threadIdx.x]
+                                                : 0.f;
+  };
+  int v = blockIdx.x;
+  if (v >= tiles) return;
+  fetch(v, 0);
+  for (; v < tiles; v += gridDim.x) {
+    int t = conv2_xcd_tile(v, tiles);
+    int nb = t % 9;
+    long long g = t / 9;
+    int ci0 = nb * 32 / 9;
+    int boff[2];
     #pragma unroll
-    for (int y = 0; y < C2W_ROWS; ++y)
+    for (int q = 0; q < 2; ++q) {
+      int n = nb * 32 + q * 16 + il;
+      int ci = n / 9, rem = n % 9;
+      boff[q] = (ci - ci0) * C2W_PS + (rem / 3) * 26 + rem % 3 + kc;
+    }
+    f32x4 acc[2][2];
+    acc[0][0] = acc[0][1] = acc[1][0] = acc[1][1] = f32x4{0, 0, 0, 0};
+    #pragma unroll 1
+    for (int c = 0; c < C2W_NCH; ++c) {
+      __syncthreads();
       #pragma unroll
-      for (int s = 0; s < 6; ++s) {
-        float a0 = dzl[aoff[0] + y * 24 + 4 * s];
-        float a1v = dzl[aoff[1] + y * 24 + 4 * s];
-        float b0 = apl[boff[0] + y * 26 + 4 * s];
-        float b1 = apl[boff[1] + y * 26 + 4 * s];
-        acc[0][0] =
-            __builtin_amdgcn_mfma_f32_16x16x4f32(a0, b0, acc[0][0], 0, 0, 0);
-        acc[0][1] =
-            __builtin_amdgcn_mfma_f32_16x16x4f32(a0, b1, acc[0][1], 0, 0, 0);
-        acc[1][0] =
-            __builtin_amdgcn_mfma_f32_16x16x4f32(a1v, b0, acc[1][0], 0, 0, 0);
-        acc[1][1] =
-            __builtin_amdgcn_mfma_f32_16x16x4f32(a1v, b1, acc[1][1], 0, 0, 0);
+      for (int it = 0; it < 2; ++it)
+        #pragma unroll
+        for (int u = 0; u < C2W_OC / 16; ++u) {
+          float4 v = pdz[it][u];
+          float2* d2 = reinterpret_cast<float2*>(
+              dzl + (r0 + 32 * it) * C2W_LD + 4 * (sub + 4 * u));
+          d2[0] = float2{v.x, v.y};
+          d2[1] = float2{v.z, v.w};
+        }
+      if (threadIdx.x < C2W_PS) {
+        #pragma unroll
+        for (int p = 0; p < 5; ++p) apl[p * C2W_PS + threadIdx.x] = pa[p];
       }
-  }
-  float* out = slab + g * 18432;
-  #pragma unroll
-  for (int mt = 0; mt < 2; ++mt) {
-    int orow = w * 32 + mt * 16 + kc * 4;
-    #pragma unroll
-    for (int nt = 0; nt < 2; ++nt)
+      __syncthreads();
+      if (c + 1 < C2W_NCH) fetch(v, c + 1);
+      else if (v + (int)gridDim.x < tiles) fetch(v + (int)gridDim.x, 0);
       #pragma unroll
-      for (int r = 0; r < 4; ++r)
-        out[(orow + r) * 288 + nb * 32 + nt * 16 + il] = acc[mt][nt][r];
+      for (int y = 0; y < C2W_ROWS; ++y)
+        #pragma unroll
+        for (int s = 0; s < 6; ++s) {
+          float a0 = dzl[aoff[0] + y * 24 + 4 * s];
+          float a1v = dzl[aoff[1] + y * 24 + 4 * s];
+          float b0 = apl[boff[0] + y * 26 + 4 * s];
+          float b1 = apl[boff[1] + y * 26 + 4 * s];
+          acc[0][0] =
+              __builtin_amdgcn_mfma_f32_16x16x4f32(a0, b0, acc[0][0], 0, 0, 0);
+          acc[0][1] =
+              __builtin_amdgcn_mfma_f32_16x16x4f32(a0, b1, acc[0][1], 0, 0, 0);
+          acc[1][0] =
+              __builtin_amdgcn_mfma_f32_16x16x4f32(a1v, b0, acc[1][0], 0, 0, 0);
+          acc[1][1] =
+              __builtin_amdgcn_mfma_f32_16x16x4f32(a1v, b1, acc[1][1], 0, 0, 0);
+        }
+    }
+    float* out = slab + g * 18432;
+    #pragma unroll
+    for (int mt = 0; mt < 2; ++mt) {
+      int orow = w * 32 + mt * 16 + kc * 4;
+      #pragma unroll
+      for (int nt = 0; nt < 2; ++nt)
+        #pragma unroll
+        for (int r = 0; r < 4; ++r)
+          out[(orow + r) * 288 + nb * 32 + nt * 16 + il] = acc[mt][nt][r];
+    }
   }
 }
 
@@ -1286,6 +1336,14 @@ void k_conv2_bwd_x_mfma_mb(const float* __restrict__ dz2,
       *reinterpret_cast<float4*>(dz1 + o) = v;
     }
   }
+}
+
+// grid of the backward-weights tile loop for G images (one occupancy
+// query per process)
+static int conv2_bwd_w_grid(int G, int max_blocks) {
+  static int resident = 0;
+  return conv2_grid(reinterpret_cast<const void*>(k_conv2_bwd_w_mfma_mb),
+                    128, 9LL * G, max_blocks, &resident);
 }
 
 __global__ void k_conv1_bwd_w_mb(const float* __restrict__ x,
@@ -2059,8 +2117,8 @@ static void cnn_step(const float* shard_x, const long long* shard_y,
     STEP(k_conv2_bwd_w_mfma_mb_bf16, dim3(18 * G), dim3(FBLK), 0, ws.dz2,
          ws.a1, bs, K, ws.wsl);
   } else {
-    STEP(k_conv2_bwd_w_mfma_mb, dim3(9 * G), dim3(128), 0, ws.dz2, ws.a1, bs,
-         K, ws.wsl);
+    STEP(k_conv2_bwd_w_mfma_mb, dim3(conv2_bwd_w_grid(G, 0)), dim3(128), 0,
+         ws.dz2, ws.a1, bs, K, ws.wsl);
   }
   STEP(k_conv2_bwd_w_fold_mb, w2_grid, dim3(FBLK), 0, ws.wsl, grads, P, o.w2,
        bs, K);
@@ -2348,8 +2406,9 @@ static void conv2_bwd_w_tail(const float* dz2, const float* slab, int bs,
 }
 void launch_conv2_bwd_w_mfma(const float* dz2, const float* a1, int bs, int K,
                              float* slab, float* dw2, float* db2,
-                             hipStream_t s) {
-  hipLaunchKernelGGL(k_conv2_bwd_w_mfma_mb, dim3(9 * K * bs), dim3(128), 0,
+                             int max_blocks, hipStream_t s) {
+  hipLaunchKernelGGL(k_conv2_bwd_w_mfma_mb,
+                     dim3(conv2_bwd_w_grid(K * bs, max_blocks)), dim3(128), 0,
                      s, dz2, a1, bs, K, slab);
   conv2_bwd_w_tail(dz2, slab, bs, K, dw2, db2, s);
 }

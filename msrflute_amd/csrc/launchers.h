@@ -300,9 +300,12 @@ void launch_pool_drop_bwd_bias(const float* da2, const unsigned char* pidx,
 void launch_conv2_bwd_x_mfma(const float* dz2, const float* w2rot,
                              const float* a1, int bs, int K, float* dz1,
                              hipStream_t s);
+// The backward-weights kernel walks its K*bs*9 tiles of 32 columns with
+// min(tiles, resident blocks) blocks; max_blocks > 0 caps that grid, 0
+// leaves it to the occupancy query.  The result does not depend on it.
 void launch_conv2_bwd_w_mfma(const float* dz2, const float* a1, int bs,
                              int K, float* slab, float* dw2, float* db2,
-                             hipStream_t s);
+                             int max_blocks, hipStream_t s);
 void launch_fc1_fwd_mfma(const float* a2, const float* w3, const float* b3,
                          int bs, int K, float p2, unsigned long long seed,
                          unsigned long long offset, float* slab, float* z3,
