@@ -15,7 +15,12 @@ SDPA (PERF.md, "Short-sequence attention").
 ``model_config.fused_pooling: true`` runs the three attentive poolings as
 ``fused_attentive_pool`` (csrc/attn_pool.hip: one launch forward and one
 backward on the fp32 MFMA; L <= 64, D <= 512, hidden <= 256, float32 on the
-GPU); off by default (PERF.md, "Attentive pooling").  The embedding matrix is
+GPU); off by default (PERF.md, "Attentive pooling").
+``model_config.fused_conv: true`` runs the title convolution and its ReLU as
+``fused_conv1d_relu`` (csrc/conv1d_seq.hip: one launch forward and one
+backward on the fp32 MFMA, on [B, T, E] rows as they are, no transposed
+views; T <= 64, channels <= 512, kernel width <= 5, float32 on the GPU); off
+by default (PERF.md, "Title convolution").  The embedding matrix is
 random-init frozen
 (no GloVe download offline — pass ``embedding_path`` to a local ``.npy``
 to load real vectors); metrics are computed in torch (no sklearn/nltk);
@@ -38,6 +43,8 @@ from msrflute_amd.core.model import BaseModel
 from msrflute_amd.ops.attention import (fused_attentive_pool,
                                         fused_attentive_pool_available,
                                         fused_mha, fused_mha_available)
+from msrflute_amd.ops.conv1d import (fused_conv1d_relu,
+                                     fused_conv1d_relu_available)
 from msrflute_amd.ops.lstm import FusedGRU
 from msrflute_amd.utils import to_device
 
@@ -99,10 +106,15 @@ class SelfAttention(nn.Module):
 
 class DocEncoder(nn.Module):
     """Title encoder: conv over words -> self-attn -> attentive pooling
-    (reference fednewsrec_model.py:128-197)."""
+    (reference fednewsrec_model.py:128-197).  With ``fused_conv`` set the
+    conv and its ReLU are ``fused_conv1d_relu`` on ``conv``'s own parameters
+    where ``fused_conv1d_relu_available`` says so; both dropouts stay torch
+    ops around it."""
 
-    def __init__(self, embed_dim=300, conv_dim=400, heads=20):
+    def __init__(self, embed_dim=300, conv_dim=400, heads=20,
+                 fused_conv=False):
         super().__init__()
+        self.fused_conv = fused_conv
         self.drop1 = nn.Dropout(0.2)
         self.conv = nn.Conv1d(embed_dim, conv_dim, 3)
         self.drop2 = nn.Dropout(0.2)
@@ -111,8 +123,14 @@ class DocEncoder(nn.Module):
         self.pool = AttentivePooling(conv_dim)
 
     def forward(self, x):                     # [B, T, E] -> [B, D]
-        h = self.conv(self.drop1(x).transpose(1, 2)).transpose(1, 2)
-        h = self.drop2(F.relu(h))
+        x, conv = self.drop1(x), self.conv
+        if self.fused_conv and fused_conv1d_relu_available(
+                x.shape[1], conv.in_channels, conv.out_channels,
+                conv.kernel_size[0], x):
+            h = fused_conv1d_relu(x, conv.weight, conv.bias)
+        else:
+            h = F.relu(conv(x.transpose(1, 2)).transpose(1, 2))
+        h = self.drop2(h)
         h = self.drop3(F.relu(self.attn(h)))
         return self.pool(h)
 
@@ -210,6 +228,8 @@ class FEDNEWS(BaseModel):
                 m.fused = bool(model_config.get("fused_attention", False))
             if isinstance(m, AttentivePooling):
                 m.fused = bool(model_config.get("fused_pooling", False))
+            if isinstance(m, DocEncoder):
+                m.fused_conv = bool(model_config.get("fused_conv", False))
 
     def loss(self, input):
         if not self.net.training:

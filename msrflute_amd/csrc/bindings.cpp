@@ -831,6 +831,68 @@ std::vector<torch::Tensor> attn_pool_bwd(torch::Tensor x, torch::Tensor e,
   return {dx, dz, da};
 }
 
+// fused Conv1d + bias + ReLU on [N, T, C] rows (conv1d_seq.hip): fp32,
+// stride 1, no padding, 1 <= KW <= 5, KW <= T <= 64, Cin % 4 == 0 with
+// 4 <= Cin <= 512, Cout % 4 == 0 with 4 <= Cout <= 512.  wp is the packed
+// weight [KW, Cout, Cin], wp[k][c][e] = weight[c][e][k].
+static void conv1d_check(const torch::Tensor& wp, long long T) {
+  check_flat(wp, "wp");
+  TORCH_CHECK(wp.dim() == 3, "wp must be [KW, Cout, Cin]");
+  long long KW = wp.size(0), Cout = wp.size(1), Cin = wp.size(2);
+  TORCH_CHECK(KW >= 1 && KW <= 5,
+              "the fused conv1d supports 1 <= KW <= 5, got KW = ", KW);
+  TORCH_CHECK(T >= KW && T <= 64,
+              "the fused conv1d supports KW <= T <= 64, got T = ", T,
+              " at KW = ", KW);
+  TORCH_CHECK(Cin % 4 == 0 && Cin >= 4 && Cin <= 512,
+              "the fused conv1d supports Cin % 4 == 0 and 4 <= Cin <= 512, "
+              "got Cin = ", Cin);
+  TORCH_CHECK(Cout % 4 == 0 && Cout >= 4 && Cout <= 512,
+              "the fused conv1d supports Cout % 4 == 0 and "
+              "4 <= Cout <= 512, got Cout = ", Cout);
+  pool_tensor(wp, "wp", wp.sizes(), "[KW, Cout, Cin]");
+}
+
+torch::Tensor conv1d_relu_fwd(torch::Tensor x, torch::Tensor wp,
+                              torch::Tensor bias) {
+  check_flat(x, "x");
+  TORCH_CHECK(x.dim() == 3, "x must be [N, T, Cin]");
+  conv1d_check(wp, x.size(1));
+  long long N = x.size(0), T = x.size(1);
+  long long KW = wp.size(0), Cout = wp.size(1), Cin = wp.size(2);
+  pool_tensor(x, "x", {N, T, Cin}, "[N, T, Cin]");
+  pool_tensor(bias, "bias", {Cout}, "[Cout]");
+  auto y = torch::empty({N, T - KW + 1, Cout}, x.options());
+  if (N > 0)
+    launch_conv1d_relu_fwd(x.data_ptr<float>(), wp.data_ptr<float>(),
+                           bias.data_ptr<float>(), y.data_ptr<float>(),
+                           (int)N, (int)T, (int)Cin, (int)Cout, (int)KW,
+                           cur_stream());
+  return y;
+}
+
+std::vector<torch::Tensor> conv1d_relu_bwd(torch::Tensor y, torch::Tensor wp,
+                                           torch::Tensor dy, bool need_dx) {
+  check_flat(y, "y");
+  TORCH_CHECK(y.dim() == 3 && y.size(1) >= 1, "y must be [N, Lout, Cout]");
+  TORCH_CHECK(wp.dim() == 3, "wp must be [KW, Cout, Cin]");
+  long long N = y.size(0), Lout = y.size(1);
+  long long KW = wp.size(0), Cout = wp.size(1), Cin = wp.size(2);
+  long long T = Lout + KW - 1;
+  conv1d_check(wp, T);
+  pool_tensor(y, "y", {N, Lout, Cout}, "[N, Lout, Cout]");
+  pool_tensor(dy, "dy", {N, Lout, Cout}, "[N, Lout, Cout]");
+  auto dx = torch::empty({need_dx ? N : 0, T, Cin}, y.options());
+  auto dz = torch::empty({N, T, Cout}, y.options());
+  if (N > 0)
+    launch_conv1d_relu_bwd(y.data_ptr<float>(), wp.data_ptr<float>(),
+                           dy.data_ptr<float>(),
+                           need_dx ? dx.data_ptr<float>() : nullptr,
+                           dz.data_ptr<float>(), (int)N, (int)T, (int)Cin,
+                           (int)Cout, (int)KW, need_dx ? 1 : 0, cur_stream());
+  return {dx, dz};
+}
+
 // fused GRU gate math (no-grad eval path of the nlg_gru recurrence)
 torch::Tensor gru_gates(torch::Tensor g_i, torch::Tensor g_h,
                         torch::Tensor h) {
@@ -1374,5 +1436,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("mha_small_bwd", &mha_small_bwd);
   m.def("attn_pool_fwd", &attn_pool_fwd);
   m.def("attn_pool_bwd", &attn_pool_bwd);
+  m.def("conv1d_relu_fwd", &conv1d_relu_fwd);
+  m.def("conv1d_relu_bwd", &conv1d_relu_bwd);
   m.def("lstm_seq_bwd", &lstm_seq_bwd);
 }

@@ -210,6 +210,21 @@ void launch_attn_pool_bwd(const float* x, const float* e, const float* p,
                           float* dx, float* dz, float* da, int N, int L,
                           int D, int Hd, hipStream_t s);
 
+// conv1d_seq.hip — fused Conv1d + bias + ReLU on [N, T, C] rows for
+// 1 <= KW <= 5, KW <= T <= 64, Cin % 4 == 0 with 4 <= Cin <= 512,
+// Cout % 4 == 0 with 4 <= Cout <= 512 (checked by the bindings), fp32,
+// stride 1, no padding, everything contiguous and 16-byte aligned:
+// x, dx [N, T, Cin]; wp [KW, Cout, Cin] (wp[k][c][e] = weight[c][e][k]);
+// bias [Cout]; y, dy [N, T - KW + 1, Cout]; dz_pad [N, T, Cout], the
+// gradient at the pre-activation with zero rows at t > T - KW.  dx is not
+// written (and may be null) when need_dx == 0.
+void launch_conv1d_relu_fwd(const float* x, const float* wp,
+                            const float* bias, float* y, int N, int T,
+                            int Cin, int Cout, int KW, hipStream_t s);
+void launch_conv1d_relu_bwd(const float* y, const float* wp, const float* dy,
+                            float* dx, float* dz_pad, int N, int T, int Cin,
+                            int Cout, int KW, int need_dx, hipStream_t s);
+
 // fused_cnn.hip — drivers.  mu > 0 (FedProx) makes the clip/SGD tail of
 // every step use g + mu (w - server) and adds 0.5 mu ||w - server||^2 to
 // the step's loss, for the clients active at that step; mu == 0 launches

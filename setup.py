@@ -49,10 +49,11 @@ class Build(BuildExtension):
     attentive pooling pair (attn_pool.hip) joins them: its matrix work is
     on the MFMA pipe, what is left are scalar fmaf chains in a fixed order,
     and its tanh / exp (scalar_math.h) are the code the LSTM kernels
-    compile without packed pairs."""
+    compile without packed pairs.  So does the title convolution pair
+    (conv1d_seq.hip): MFMA chains and a scalar bias / max epilogue."""
 
     NO_PACKED_FP32 = ("gru_seq_bf16", "gru_seq_any", "mha_small",
-                      "attn_pool")
+                      "attn_pool", "conv1d_seq")
 
     def build_extensions(self):
         os.makedirs(self.build_temp, exist_ok=True)
