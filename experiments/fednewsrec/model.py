@@ -17,10 +17,12 @@ SDPA (PERF.md, "Short-sequence attention").
 backward on the fp32 MFMA; L <= 64, D <= 512, hidden <= 256, float32 on the
 GPU); off by default (PERF.md, "Attentive pooling").
 ``model_config.fused_conv: true`` runs the title convolution and its ReLU as
-``fused_conv1d_relu`` (csrc/conv1d_seq.hip: one launch forward and one
-backward on the fp32 MFMA, on [B, T, E] rows as they are, no transposed
-views; T <= 64, channels <= 512, kernel width <= 5, float32 on the GPU); off
-by default (PERF.md, "Title convolution").  The embedding matrix is
+``fused_conv1d_relu`` (csrc/conv1d_seq.hip: one launch forward on the fp32
+MFMA, on [B, T, E] rows as they are, no transposed views; backward, with the
+embedding frozen, csrc/conv1d_bwd_w.hip's split-K weight-gradient kernel
+and its fold, two launches and no library GEMM; T <= 64, channels <= 512,
+kernel width <= 5, float32 on the GPU); off by default (PERF.md, "Title
+convolution: backward-weights").  The embedding matrix is
 random-init frozen
 (no GloVe download offline — pass ``embedding_path`` to a local ``.npy``
 to load real vectors); metrics are computed in torch (no sklearn/nltk);

@@ -835,10 +835,8 @@ std::vector<torch::Tensor> attn_pool_bwd(torch::Tensor x, torch::Tensor e,
 // stride 1, no padding, 1 <= KW <= 5, KW <= T <= 64, Cin % 4 == 0 with
 // 4 <= Cin <= 512, Cout % 4 == 0 with 4 <= Cout <= 512.  wp is the packed
 // weight [KW, Cout, Cin], wp[k][c][e] = weight[c][e][k].
-static void conv1d_check(const torch::Tensor& wp, long long T) {
-  check_flat(wp, "wp");
-  TORCH_CHECK(wp.dim() == 3, "wp must be [KW, Cout, Cin]");
-  long long KW = wp.size(0), Cout = wp.size(1), Cin = wp.size(2);
+static void conv1d_ranges(long long KW, long long T, long long Cin,
+                          long long Cout) {
   TORCH_CHECK(KW >= 1 && KW <= 5,
               "the fused conv1d supports 1 <= KW <= 5, got KW = ", KW);
   TORCH_CHECK(T >= KW && T <= 64,
@@ -850,6 +848,12 @@ static void conv1d_check(const torch::Tensor& wp, long long T) {
   TORCH_CHECK(Cout % 4 == 0 && Cout >= 4 && Cout <= 512,
               "the fused conv1d supports Cout % 4 == 0 and "
               "4 <= Cout <= 512, got Cout = ", Cout);
+}
+
+static void conv1d_check(const torch::Tensor& wp, long long T) {
+  check_flat(wp, "wp");
+  TORCH_CHECK(wp.dim() == 3, "wp must be [KW, Cout, Cin]");
+  conv1d_ranges(wp.size(0), T, wp.size(2), wp.size(1));
   pool_tensor(wp, "wp", wp.sizes(), "[KW, Cout, Cin]");
 }
 
@@ -891,6 +895,44 @@ std::vector<torch::Tensor> conv1d_relu_bwd(torch::Tensor y, torch::Tensor wp,
                            dz.data_ptr<float>(), (int)N, (int)T, (int)Cin,
                            (int)Cout, (int)KW, need_dx ? 1 : 0, cur_stream());
   return {dx, dz};
+}
+
+// the same convolution's dW [Cout, Cin, KW] and db [Cout] from x, y and dy
+// as they are (conv1d_bwd_w.hip): split-K over the N T flat rows, then a
+// fold; the partials are allocated here.
+static int64_t conv1d_bwd_w_slabs_py(int64_t N, int64_t T) {
+  TORCH_CHECK(N >= 0 && T >= 1);
+  return conv1d_bwd_w_slabs(N, T);
+}
+
+std::vector<torch::Tensor> conv1d_relu_bwd_w(torch::Tensor x, torch::Tensor y,
+                                             torch::Tensor dy, int64_t KW) {
+  check_flat(x, "x");
+  check_flat(y, "y");
+  TORCH_CHECK(x.dim() == 3, "x must be [N, T, Cin]");
+  TORCH_CHECK(y.dim() == 3, "y must be [N, T - KW + 1, Cout]");
+  long long N = x.size(0), T = x.size(1), Cin = x.size(2), Cout = y.size(2);
+  conv1d_ranges(KW, T, Cin, Cout);
+  long long Lout = T - KW + 1, S = conv1d_bwd_w_slabs(N, T);
+  TORCH_CHECK(N * T <= INT_MAX - 4096 && S <= 65535,
+              "the fused conv1d backward-weights supports up to ",
+              65535LL * CONV1D_BWD_W_SLAB, " rows, got N T = ", N * T);
+  pool_tensor(x, "x", {N, T, Cin}, "[N, T, Cin]");
+  pool_tensor(y, "y", {N, Lout, Cout}, "[N, T - KW + 1, Cout]");
+  pool_tensor(dy, "dy", {N, Lout, Cout}, "[N, T - KW + 1, Cout]");
+  if (N == 0)
+    return {torch::zeros({Cout, Cin, KW}, x.options()),
+            torch::zeros({Cout}, x.options())};
+  auto dW = torch::empty({Cout, Cin, KW}, x.options());
+  auto db = torch::empty({Cout}, x.options());
+  auto part = torch::empty({S, KW, Cout, Cin}, x.options());
+  auto dbpart = torch::empty({S, Cout}, x.options());
+  launch_conv1d_bwd_w(x.data_ptr<float>(), y.data_ptr<float>(),
+                      dy.data_ptr<float>(), part.data_ptr<float>(),
+                      dbpart.data_ptr<float>(), dW.data_ptr<float>(),
+                      db.data_ptr<float>(), (int)N, (int)T, (int)Cin,
+                      (int)Cout, (int)KW, cur_stream());
+  return {dW, db};
 }
 
 // fused GRU gate math (no-grad eval path of the nlg_gru recurrence)
@@ -1438,5 +1480,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("attn_pool_bwd", &attn_pool_bwd);
   m.def("conv1d_relu_fwd", &conv1d_relu_fwd);
   m.def("conv1d_relu_bwd", &conv1d_relu_bwd);
+  m.def("conv1d_relu_bwd_w", &conv1d_relu_bwd_w);
+  m.def("conv1d_bwd_w_slabs", &conv1d_bwd_w_slabs_py);
+  m.attr("CONV1D_BWD_W_SLAB") = CONV1D_BWD_W_SLAB;
   m.def("lstm_seq_bwd", &lstm_seq_bwd);
 }

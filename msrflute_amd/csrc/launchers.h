@@ -225,6 +225,23 @@ void launch_conv1d_relu_bwd(const float* y, const float* wp, const float* dy,
                             float* dx, float* dz_pad, int N, int T, int Cin,
                             int Cout, int KW, int need_dx, hipStream_t s);
 
+// conv1d_bwd_w.hip — the same convolution's weight and bias gradients, in
+// the same ranges, read from x, y and dy as they are: dW [Cout, Cin, KW]
+// (nn.Conv1d's layout), db [Cout].  Split-K over the N T flat rows in slabs
+// of CONV1D_BWD_W_SLAB rows: part [S, KW, Cout, Cin] and dbpart [S, Cout]
+// with S = conv1d_bwd_w_slabs(N, T) are workspace the caller allocates; a
+// second kernel folds them, slabs ascending.  N >= 1.
+#ifndef CONV1D_BWD_W_SLAB
+#define CONV1D_BWD_W_SLAB 384
+#endif
+inline long long conv1d_bwd_w_slabs(long long N, long long T) {
+  return (N * T + CONV1D_BWD_W_SLAB - 1) / CONV1D_BWD_W_SLAB;
+}
+void launch_conv1d_bwd_w(const float* x, const float* y, const float* dy,
+                         float* part, float* dbpart, float* dW, float* db,
+                         int N, int T, int Cin, int Cout, int KW,
+                         hipStream_t s);
+
 // fused_cnn.hip — drivers.  mu > 0 (FedProx) makes the clip/SGD tail of
 // every step use g + mu (w - server) and adds 0.5 mu ||w - server||^2 to
 // the step's loss, for the clients active at that step; mu == 0 launches

@@ -5,10 +5,11 @@
 stride-1, unpadded ``nn.Conv1d``, computed in the layout the rest of a
 sequence model uses: ``x [N, T, Cin]`` in, ``y [N, T - KW + 1, Cout]`` out,
 both contiguous, no transposed view on either side.  One launch forward on
-the fp32 MFMA with bias and ReLU in its epilogue; one launch backward that
-applies the ReLU mask and gives ``dx`` (skipped when ``x`` needs no
-gradient) and the padded pre-activation gradient ``dz_pad [N, T, Cout]``,
-from which the weight and bias gradients are library GEMMs.
+the fp32 MFMA with bias and ReLU in its epilogue.  Backward, the weight and
+bias gradients are a split-K MFMA kernel over the flat rows and its fold
+(csrc/conv1d_bwd_w.hip), which read ``x``, ``y`` and ``dy`` as they are and
+write ``dW`` in ``nn.Conv1d``'s layout; ``dx`` is one more launch, made only
+when ``x`` needs a gradient.
 """
 
 import torch
@@ -39,12 +40,12 @@ def _conv1d_pack(weight):
 
 
 class _Conv1dReLU(torch.autograd.Function):
-    """Saves x, y and the packed weight.  The backward kernel gives dx and
-    ``dz_pad``, the gradient at the pre-activation on T rows per sequence
-    with the rows t > T - KW exactly zero.  On the flat rows r = n T + t
-    those zero rows make ``dW[:, :, k] = dz[0 : R - k]^T x[k : R]`` free of
-    cross-sequence terms; with ``db = sum_r dz`` these are library work, as
-    in the recurrences."""
+    """Saves x, y and the packed weight.  With ``dz = dy (y > 0)`` on T rows
+    per sequence, the rows t > T - KW exactly zero, and the flat rows
+    r = n T + t, ``dW[:, :, k] = dz[0 : R - k]^T x[k : R]`` is free of
+    cross-sequence terms and ``db = sum_r dz``: ``_C.conv1d_relu_bwd_w``
+    computes both from x, y and dy, masking while it stages.  Without ``dx``
+    that is the whole backward."""
 
     @staticmethod
     def forward(ctx, x, weight, bias):
@@ -56,13 +57,11 @@ class _Conv1dReLU(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         x, y, wp = ctx.saved_tensors
-        dx, dz = _C.conv1d_relu_bwd(y, wp, _aligned(dy),
-                                    ctx.needs_input_grad[0])
-        dz, xf = dz.flatten(0, 1), x.flatten(0, 1)
-        R = xf.shape[0]
-        dw = torch.stack([dz[:R - k].t() @ xf[k:]
-                          for k in range(wp.shape[0])], dim=2)
-        return (dx if ctx.needs_input_grad[0] else None), dw, dz.sum(0)
+        dy = _aligned(dy)
+        dw, db = _C.conv1d_relu_bwd_w(x, y, dy, wp.shape[0])
+        dx = _C.conv1d_relu_bwd(y, wp, dy, True)[0] \
+            if ctx.needs_input_grad[0] else None
+        return dx, dw, db
 
 
 def fused_conv1d_relu(x, weight, bias):

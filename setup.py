@@ -50,10 +50,12 @@ class Build(BuildExtension):
     on the MFMA pipe, what is left are scalar fmaf chains in a fixed order,
     and its tanh / exp (scalar_math.h) are the code the LSTM kernels
     compile without packed pairs.  So does the title convolution pair
-    (conv1d_seq.hip): MFMA chains and a scalar bias / max epilogue."""
+    (conv1d_seq.hip): MFMA chains and a scalar bias / max epilogue.  Its
+    backward-weights pair (conv1d_bwd_w.hip) is MFMA chains, a scalar db
+    chain and a fold whose adds run in a fixed order."""
 
     NO_PACKED_FP32 = ("gru_seq_bf16", "gru_seq_any", "mha_small",
-                      "attn_pool", "conv1d_seq")
+                      "attn_pool", "conv1d_seq", "conv1d_bwd_w")
 
     def build_extensions(self):
         os.makedirs(self.build_temp, exist_ok=True)
