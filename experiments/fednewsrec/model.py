@@ -10,8 +10,12 @@ MI355X-native divergences: multi-head attention uses
 ``model_config.fused_attention: true`` runs it as ``fused_mha``
 (csrc/mha_small.hip: one launch forward and one backward on the projection
 GEMMs' own [B, L, heads*d] layout; L <= 64, d <= 32, float32 on the GPU).
-It is off by default: measured at the task's shapes it is not faster than
-SDPA (PERF.md, "Short-sequence attention").
+``model_config.fused_attention: mfma`` runs it as ``fused_mha(...,
+impl="mfma")`` (csrc/mha_mfma.hip: the same range and layout, one wave per
+(sequence, head) on the fp32 MFMA, nothing saved but q, k, v).
+Both are off by default: ``mha_small`` is not faster than SDPA at the task's
+shapes (PERF.md, "Short-sequence attention"); for the MFMA pair see PERF.md,
+"Short-sequence attention on the MFMA".
 ``model_config.fused_pooling: true`` runs the three attentive poolings as
 ``fused_attentive_pool`` (csrc/attn_pool.hip: one launch forward and one
 backward on the fp32 MFMA; L <= 64, D <= 512, hidden <= 256, float32 on the
@@ -82,7 +86,8 @@ class SelfAttention(nn.Module):
     """Multi-head self-attention via SDPA (reference Attention module,
     fednewsrec_model.py:44-106, was einsum-based).  With ``fused`` set it is
     ``fused_mha`` on the three projections where ``fused_mha_available``
-    says so, and SDPA on head views otherwise."""
+    says so, and SDPA on head views otherwise; ``fused="mfma"`` selects
+    ``impl="mfma"``, any other true value the default ``impl="lanes"``."""
 
     def __init__(self, dim, heads, head_dim, fused=False):
         super().__init__()
@@ -98,7 +103,8 @@ class SelfAttention(nn.Module):
     def forward(self, x):                     # [B, L, D] -> [B, L, H*Hd]
         B, L, _ = x.shape
         if self.fused and fused_mha_available(L, self.head_dim, x):
-            return fused_mha(self.wq(x), self.wk(x), self.wv(x), self.heads)
+            return fused_mha(self.wq(x), self.wk(x), self.wv(x), self.heads,
+                             impl="mfma" if self.fused == "mfma" else "lanes")
         q = self.wq(x).view(B, L, self.heads, self.head_dim).transpose(1, 2)
         k = self.wk(x).view(B, L, self.heads, self.head_dim).transpose(1, 2)
         v = self.wv(x).view(B, L, self.heads, self.head_dim).transpose(1, 2)
@@ -227,7 +233,8 @@ class FEDNEWS(BaseModel):
             model_config.get("freeze_embeddings", True)))
         for m in self.net.modules():
             if isinstance(m, SelfAttention):
-                m.fused = bool(model_config.get("fused_attention", False))
+                fused = model_config.get("fused_attention", False)
+                m.fused = "mfma" if fused == "mfma" else bool(fused)
             if isinstance(m, AttentivePooling):
                 m.fused = bool(model_config.get("fused_pooling", False))
             if isinstance(m, DocEncoder):

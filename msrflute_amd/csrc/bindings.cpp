@@ -757,6 +757,42 @@ std::vector<torch::Tensor> mha_small_bwd(torch::Tensor q, torch::Tensor k,
   return {dq, dk, dv};
 }
 
+// the same attention on the fp32 MFMA (mha_mfma.hip): same range, same
+// layouts, nothing saved but q, k, v
+torch::Tensor mha_mfma_fwd(torch::Tensor q, torch::Tensor k, torch::Tensor v,
+                           int64_t heads) {
+  long long S = mha_check(q, k, v, heads);
+  long long N = q.size(0), L = q.size(1), E = q.size(2);
+  auto o = torch::empty({N, L, E}, q.options());
+  if (N > 0)
+    launch_mha_mfma_fwd(q.data_ptr<float>(), k.data_ptr<float>(),
+                        v.data_ptr<float>(), o.data_ptr<float>(), (int)N,
+                        (int)L, (int)heads, (int)(E / heads), S,
+                        cur_stream());
+  return o;
+}
+
+std::vector<torch::Tensor> mha_mfma_bwd(torch::Tensor q, torch::Tensor k,
+                                        torch::Tensor v, torch::Tensor d_o,
+                                        int64_t heads) {
+  long long S = mha_check(q, k, v, heads);
+  check_flat(d_o, "do");
+  TORCH_CHECK(d_o.sizes() == q.sizes() &&
+              reinterpret_cast<uintptr_t>(d_o.data_ptr()) % 16 == 0,
+              "do must be contiguous [N, L, heads*d], 16-byte aligned");
+  long long N = q.size(0), L = q.size(1), E = q.size(2);
+  auto dq = torch::empty({N, L, E}, q.options());
+  auto dk = torch::empty({N, L, E}, q.options());
+  auto dv = torch::empty({N, L, E}, q.options());
+  if (N > 0)
+    launch_mha_mfma_bwd(q.data_ptr<float>(), k.data_ptr<float>(),
+                        v.data_ptr<float>(), d_o.data_ptr<float>(),
+                        dq.data_ptr<float>(), dk.data_ptr<float>(),
+                        dv.data_ptr<float>(), (int)N, (int)L, (int)heads,
+                        (int)(E / heads), S, cur_stream());
+  return {dq, dk, dv};
+}
+
 // fused attentive pooling (attn_pool.hip): fp32, 1 <= L <= 64, D % 4 == 0
 // with 4 <= D <= 512, Hd % 4 == 0 with 4 <= Hd <= 256.  w1 is dense.weight
 // [Hd, D] as it is (no packed layout), w2 is dense2.weight as [Hd].
@@ -1476,6 +1512,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gru_seq_any_bwd", &gru_seq_any_bwd);
   m.def("mha_small_fwd", &mha_small_fwd);
   m.def("mha_small_bwd", &mha_small_bwd);
+  m.def("mha_mfma_fwd", &mha_mfma_fwd);
+  m.def("mha_mfma_bwd", &mha_mfma_bwd);
   m.def("attn_pool_fwd", &attn_pool_fwd);
   m.def("attn_pool_bwd", &attn_pool_bwd);
   m.def("conv1d_relu_fwd", &conv1d_relu_fwd);

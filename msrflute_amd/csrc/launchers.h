@@ -196,6 +196,16 @@ void launch_mha_small_bwd(const float* q, const float* k, const float* v,
                           float* dq, float* dk, float* dv, int N, int L,
                           int heads, int d, long long S, hipStream_t s);
 
+// mha_mfma.hip — the same range and layouts on the fp32 MFMA, one wave per
+// (sequence, head); no lse: the backward reads q, k, v, d_o only
+void launch_mha_mfma_fwd(const float* q, const float* k, const float* v,
+                         float* o, int N, int L, int heads, int d,
+                         long long S, hipStream_t s);
+void launch_mha_mfma_bwd(const float* q, const float* k, const float* v,
+                         const float* d_o, float* dq, float* dk, float* dv,
+                         int N, int L, int heads, int d, long long S,
+                         hipStream_t s);
+
 // attn_pool.hip — fused attentive pooling for 1 <= L <= 64, D % 4 == 0 with
 // 4 <= D <= 512, Hd % 4 == 0 with 4 <= Hd <= 256 (checked by the bindings),
 // fp32, everything contiguous and 16-byte aligned: x, dx [N, L, D];

@@ -1,10 +1,14 @@
-"""Fused multi-head attention for short sequences (csrc/mha_small.hip).
+"""Fused multi-head attention for short sequences (csrc/mha_small.hip,
+csrc/mha_mfma.hip).
 
 ``fused_mha(q, k, v, heads)`` is ``softmax(q k^T / sqrt(d)) v`` per head on
 ``[N, L, heads*d]`` tensors in the layout the projection GEMMs produce: no
 ``[N, heads, L, d]`` view or copy on the way in or out, no mask, no dropout,
 not causal.  One launch forward, one backward.  q, k and v may be
 contiguous or three slices of one ``[N, L, 3*heads*d]`` buffer.
+``impl="lanes"`` (the default) gives a lane one query row (mha_small.hip);
+``impl="mfma"`` gives a wave one (sequence, head) problem on the fp32 MFMA
+(mha_mfma.hip) and saves nothing but q, k and v.
 
 ``fused_attentive_pool(x, w1, b1, w2, b2)`` is additive attention pooling
 (csrc/attn_pool.hip): ``softmax_L(tanh(x w1^T + b1) . w2 + b2)``-weighted
@@ -59,12 +63,42 @@ class _MHASmall(torch.autograd.Function):
         return dq, dk, dv, None
 
 
-def fused_mha(q, k, v, heads):
-    """[N, L, heads*d] x 3 -> [N, L, heads*d], scale 1/sqrt(d).  Raises when
-    the shape, dtype or device is not one ``fused_mha_available`` accepts."""
+class _MHAMfma(torch.autograd.Function):
+    """Saves q, k, v only: the backward recomputes the scores, the row
+    maxima and sums with the forward's instructions, and takes
+    D = sum_j P dP from its registers, so neither o nor an lse is read."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, heads):
+        q, k, v = _rows(q), _rows(k), _rows(v)
+        if not (q.stride() == k.stride() == v.stride()):
+            q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
+        ctx.save_for_backward(q, k, v)
+        ctx.heads = heads
+        return _C.mha_mfma_fwd(q, k, v, heads)
+
+    @staticmethod
+    def backward(ctx, do):
+        q, k, v = ctx.saved_tensors
+        dq, dk, dv = _C.mha_mfma_bwd(q, k, v, _aligned(do), ctx.heads)
+        return dq, dk, dv, None
+
+
+_IMPLS = {"lanes": _MHASmall, "mfma": _MHAMfma}
+
+
+def fused_mha(q, k, v, heads, impl="lanes"):
+    """[N, L, heads*d] x 3 -> [N, L, heads*d], scale 1/sqrt(d), by
+    mha_small.hip (``impl="lanes"``) or mha_mfma.hip (``impl="mfma"``).
+    Raises when the shape, dtype or device is not one
+    ``fused_mha_available`` accepts, and ``ValueError`` for any other
+    ``impl``."""
+    if impl not in _IMPLS:
+        raise ValueError(f"fused_mha: impl must be one of {sorted(_IMPLS)}, "
+                         f"got {impl!r}")
     if not HAS_EXT:
         raise RuntimeError("fused_mha needs the msrflute_amd._C extension")
-    return _MHASmall.apply(q, k, v, int(heads))
+    return _IMPLS[impl].apply(q, k, v, int(heads))
 
 
 def fused_attentive_pool_available(L, D, Hd, x):

@@ -52,10 +52,12 @@ class Build(BuildExtension):
     compile without packed pairs.  So does the title convolution pair
     (conv1d_seq.hip): MFMA chains and a scalar bias / max epilogue.  Its
     backward-weights pair (conv1d_bwd_w.hip) is MFMA chains, a scalar db
-    chain and a fold whose adds run in a fixed order."""
+    chain and a fold whose adds run in a fixed order.  The MFMA attention
+    pair (mha_mfma.hip) is MFMA chains and a scalar softmax in a fixed
+    order, with scalar_math.h's exp."""
 
     NO_PACKED_FP32 = ("gru_seq_bf16", "gru_seq_any", "mha_small",
-                      "attn_pool", "conv1d_seq", "conv1d_bwd_w")
+                      "attn_pool", "conv1d_seq", "conv1d_bwd_w", "mha_mfma")
 
     def build_extensions(self):
         os.makedirs(self.build_temp, exist_ok=True)
