@@ -1235,6 +1235,32 @@ torch::Tensor dbg_fc1_bwd_x_mfma(torch::Tensor dz3, torch::Tensor w3,
   return da2;
 }
 
+// norm + clip + SGD of the FedAvg mega round's tail, dW3 re-formed from
+// dz3 and a2; params / grads are [K * P] stacks of the C-class CNN
+void dbg_fc1_fused_tail(torch::Tensor params, torch::Tensor grads,
+                        torch::Tensor dz3, torch::Tensor a2, int64_t B,
+                        int64_t K, int64_t C, torch::Tensor acc,
+                        double max_norm, torch::Tensor lr_t,
+                        torch::Tensor stats) {
+  check_flat(params, "params"); check_flat(grads, "grads");
+  check_flat(dz3, "dz3"); check_flat(a2, "a2");
+  check_flat(lr_t, "lr_t"); check_flat(stats, "stats");
+  int bs = fc1_rows_per_client(B, K);
+  TORCH_CHECK(C >= 1);
+  long long P = cnn_offsets((int)C).total;
+  TORCH_CHECK(params.numel() == K * P && grads.numel() == K * P,
+              "params / grads must be [K * P] stacks");
+  TORCH_CHECK(dz3.numel() >= B * 128 && a2.numel() >= B * 9216);
+  TORCH_CHECK(acc.is_cuda() && acc.is_contiguous() &&
+              acc.scalar_type() == torch::kFloat64 && acc.numel() >= 2 * K);
+  TORCH_CHECK(lr_t.numel() >= 1 && stats.numel() >= 2 * K);
+  launch_fc1_fused_tail(params.data_ptr<float>(), grads.data_ptr<float>(),
+                        dz3.data_ptr<float>(), a2.data_ptr<float>(), bs,
+                        (int)K, (int)C, acc.data_ptr<double>(),
+                        (float)max_norm, lr_t.data_ptr<float>(),
+                        stats.data_ptr<float>(), cur_stream());
+}
+
 torch::Tensor dbg_mfma_bf16_probe(torch::Tensor A, torch::Tensor B) {
   TORCH_CHECK(A.is_cuda() && A.scalar_type() == torch::kBFloat16 &&
               A.is_contiguous() && A.numel() == 16 * 32);
@@ -1481,6 +1507,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("dbg_fc1_bwd_w_mfma", &dbg_fc1_bwd_w_mfma,
         py::arg("dz3"), py::arg("a2"), py::arg("B"), py::arg("K") = 1);
   m.def("dbg_fc1_bwd_x_mfma", &dbg_fc1_bwd_x_mfma);
+  m.def("dbg_fc1_fused_tail", &dbg_fc1_fused_tail);
   m.doc() = "msrflute_amd gfx950 flat-arena kernels";
   m.def("pseudo_grad", &pseudo_grad);
   m.def("axpy", &axpy);

@@ -774,14 +774,25 @@ __global__ void k_fc2_loss_fwd_mb(const float* __restrict__ a3,
                sm, z3 + g * 128, m3 + g * 128, p2, dz3 + g * 128);
 }
 
-// fc2 backward (weights): grid = K * ceil(C*128/256)
+// fc2 backward (weights): grid = K * ceil(C*128/256).  dz3 non-null (the
+// round without a stored dW3, which drops the fc1 backward-weights launch):
+// block 0 of every client also writes that kernel's 128 bias sums
+// db3[j] = sum_b dz3[b][j], the same b-ascending chain, at ob3.
 __global__ void k_fc2_bwd_w_mb(const float* __restrict__ dlogits,
                                const float* __restrict__ a3,
                                float* __restrict__ grads, long long P,
                                long long ow4, long long ob4, int bs, int K,
-                               int C) {
+                               int C, const float* __restrict__ dz3,
+                               long long ob3) {
   int per_k = (C * 128 + FBLK - 1) / FBLK;
   int k = blockIdx.x / per_k;
+  if (dz3 && blockIdx.x % per_k == 0 && threadIdx.x < 128) {
+    int j = threadIdx.x;
+    const float* dz = dz3 + (long long)k * bs * 128;
+    float s = 0.f;
+    for (int b = 0; b < bs; ++b) s += dz[(long long)b * 128 + j];
+    grads[(long long)k * P + ob3 + j] = s;
+  }
   int i0 = (blockIdx.x % per_k) * FBLK + threadIdx.x;
   if (i0 >= C * 128) return;
   int kk = i0 % 128, j = i0 / 128;
@@ -807,16 +818,23 @@ __global__ void k_fc2_bwd_w_mb(const float* __restrict__ dlogits,
 // VEC = 1: the dword map nt * 16 + il.
 #define FC1B_COL(VEC, g, il) ((g) * 16 * (VEC) + (VEC) * (il))
 
-// fc1 backward weights (f32 MFMA): grid = K * 144.  Block 0 of every
-// client also writes the 128 bias sums db3[j] = sum_b dz3[b][j].
+// One 128 x 64 tile of dW3 = dz3^T a2 in the registers of a 4-wave block:
+// wave w owns rows w*32 .. w*32+31, acc[tt][nt][r] is row
+// w*32 + tt*16 + (lane>>4)*4 + r and column nblk*64 + FC1B_COL(VEC, g, il)
+// + e with nt = g*VEC + e.  Every element is one MFMA chain, b ascending in
+// k-steps of 4 from an accumulator of 0, whatever VEC is.  The ONE place a
+// dW3 element is formed: backward-weights stores the tile, the fused tail
+// (k_fc1_tail_sumsq_mb / k_fc1_tail_clip_sgd_mb) sums and applies it.
 template <int VEC>
-__device__ __forceinline__ void fc1_bwd_w_body(
-    const float* __restrict__ dz, const float* __restrict__ a2k,
-    float* __restrict__ dw3, int bs, int nblk) {
+__device__ __forceinline__ void fc1_bwd_w_tile(
+    const float* __restrict__ dz, const float* __restrict__ a2k, int bs,
+    int nblk, f32x4 (&acc)[2][4]) {
   int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   int kc = lane >> 4, il = lane & 15;
-  f32x4 acc[2][4] = {{f32x4{0,0,0,0}, f32x4{0,0,0,0}, f32x4{0,0,0,0}, f32x4{0,0,0,0}},
-                     {f32x4{0,0,0,0}, f32x4{0,0,0,0}, f32x4{0,0,0,0}, f32x4{0,0,0,0}}};
+  #pragma unroll
+  for (int tt = 0; tt < 2; ++tt)
+    #pragma unroll
+    for (int nt = 0; nt < 4; ++nt) acc[tt][nt] = f32x4{0, 0, 0, 0};
   for (int k0 = 0; k0 < ((bs + 3) & ~3); k0 += 4) {
     int b = k0 + kc;
     bool kv = b < bs;
@@ -841,6 +859,18 @@ __device__ __forceinline__ void fc1_bwd_w_body(
       acc[1][nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1v, bv[nt], acc[1][nt], 0, 0, 0);
     }
   }
+}
+
+// fc1 backward weights (f32 MFMA): grid = K * 144.  Block 0 of every
+// client also writes the 128 bias sums db3[j] = sum_b dz3[b][j].
+template <int VEC>
+__device__ __forceinline__ void fc1_bwd_w_body(
+    const float* __restrict__ dz, const float* __restrict__ a2k,
+    float* __restrict__ dw3, int bs, int nblk) {
+  int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  int il = lane & 15;
+  f32x4 acc[2][4];
+  fc1_bwd_w_tile<VEC>(dz, a2k, bs, nblk, acc);
   #pragma unroll
   for (int tt = 0; tt < 2; ++tt) {
     int j = w * 32 + tt * 16 + (lane >> 4) * 4;
@@ -1536,7 +1566,7 @@ __device__ __forceinline__ float clip_scale(const double* __restrict__ acc,
 }
 
 // STORE_G: also write the clipped gradient back.  The CNN mega round
-// never reads it (the next batch-step's backward kernels and
+// (FedProx; FedAvg and DGA run the fused fc1 tail below) never reads it (the next batch-step's backward kernels and
 // k_pseudo_grad_mb overwrite the whole stack), so it runs the variant
 // without that store; the stand-alone entry keeps it.  i only grows, so
 // a thread re-derives its client and the scale when it crosses a segment
@@ -1588,6 +1618,217 @@ __global__ void k_clip_sgd_mb(float* __restrict__ params,
       params[i] -= lr * gv;
     }
   }
+}
+
+// ---------------------------------------------------------------------------
+// Fused fc1 tail (FedAvg / DGA mega round): the two passes above without a
+// stored dW3.  dW3 is 98 % of the arena and a rank-bs product, so both
+// passes re-form its 128 x 64 tiles in registers with fc1_bwd_w_tile from
+// dz3 and a2 (the value squared is the value applied) and never touch the
+// W3 segment of `grads`.  Block roles come from blockIdx: per client,
+// 144 / TILES tile blocks of TILES adjacent column tiles each, then
+// FC1T_REST_BLKS blocks over the rest of the arena, i.e. the o.w3 floats
+// before W3 and the P - o.w3 - W3N after it, read from `grads` as before.
+// The norm pass issues one f64 atomic pair per block (36 + 4 per client,
+// next to k_sumsq_mb's 37); the clip pass has no atomics and takes blocks
+// of 2 tiles.  Both splits were picked from kernel times at K = 10, bs = 20
+// (PERF.md).  No block waits for another; the norm is complete before the
+// clip because they are two launches.
+// ---------------------------------------------------------------------------
+#ifndef FC1T_NORM_TILES
+#define FC1T_NORM_TILES 4
+#endif
+#ifndef FC1T_CLIP_TILES
+#define FC1T_CLIP_TILES 2
+#endif
+#define FC1T_REST_BLKS 4
+#define FC1T_W3N (128LL * 9216)
+static_assert(144 % FC1T_NORM_TILES == 0 && 144 % FC1T_CLIP_TILES == 0,
+              "whole tile blocks per client");
+
+// index i of the arena without its W3 segment -> arena index
+__device__ __forceinline__ long long fc1t_rest_index(long long i,
+                                                     long long ow3) {
+  return i < ow3 ? i : i + FC1T_W3N;
+}
+
+__device__ __forceinline__ void fc1t_tile(const float* __restrict__ dz,
+                                          const float* __restrict__ a2k,
+                                          int bs, int nblk, int vec,
+                                          f32x4 (&t)[2][4]) {
+  if (vec == 4) fc1_bwd_w_tile<4>(dz, a2k, bs, nblk, t);
+  else if (vec == 2) fc1_bwd_w_tile<2>(dz, a2k, bs, nblk, t);
+  else fc1_bwd_w_tile<1>(dz, a2k, bs, nblk, t);
+}
+
+__global__ __launch_bounds__(FBLK)
+void k_fc1_tail_sumsq_mb(const float* __restrict__ grads, long long P,
+                         long long ow3, const float* __restrict__ dz3,
+                         const float* __restrict__ a2, int bs, int K,
+                         double* __restrict__ acc) {
+  constexpr int TB = 144 / FC1T_NORM_TILES;
+  constexpr int PER_K = TB + FC1T_REST_BLKS;
+  int k = blockIdx.x / PER_K;
+  int r = blockIdx.x % PER_K;
+  // (double)g into the sum, (double)g * (double)g into the squares, as
+  // k_sumsq_mb; 4 independent chains of each
+  double sv[4] = {0.0, 0.0, 0.0, 0.0}, qv[4] = {0.0, 0.0, 0.0, 0.0};
+  if (r < TB) {
+    const float* dz = dz3 + (long long)k * bs * 128;
+    const float* a2k = a2 + (long long)k * bs * 9216;
+    int vec = addr_vec((unsigned long long)a2k);
+    for (int u = 0; u < FC1T_NORM_TILES; ++u) {
+      f32x4 t[2][4];
+      fc1t_tile(dz, a2k, bs, r * FC1T_NORM_TILES + u, vec, t);
+      #pragma unroll
+      for (int tt = 0; tt < 2; ++tt)
+        #pragma unroll
+        for (int e = 0; e < 4; ++e)
+          #pragma unroll
+          for (int nt = 0; nt < 4; ++nt) {
+            double g = (double)t[tt][nt][e];
+            sv[nt] += g; qv[nt] += g * g;
+          }
+    }
+  } else {
+    const float* g = grads + (long long)k * P;
+    long long n = P - FC1T_W3N;
+    long long i = (long long)(r - TB) * FBLK + threadIdx.x;
+    const long long step = (long long)FC1T_REST_BLKS * FBLK;
+    for (; i + 3 * step < n; i += 4 * step) {
+      double v0 = g[fc1t_rest_index(i, ow3)];
+      double v1 = g[fc1t_rest_index(i + step, ow3)];
+      double v2 = g[fc1t_rest_index(i + 2 * step, ow3)];
+      double v3 = g[fc1t_rest_index(i + 3 * step, ow3)];
+      sv[0] += v0; qv[0] += v0 * v0;
+      sv[1] += v1; qv[1] += v1 * v1;
+      sv[2] += v2; qv[2] += v2 * v2;
+      sv[3] += v3; qv[3] += v3 * v3;
+    }
+    for (; i < n; i += step) {
+      double v = g[fc1t_rest_index(i, ow3)];
+      sv[0] += v; qv[0] += v * v;
+    }
+  }
+  double fs = (sv[0] + sv[1]) + (sv[2] + sv[3]);
+  double fq = (qv[0] + qv[1]) + (qv[2] + qv[3]);
+  for (int d = 32; d > 0; d >>= 1) {
+    fs += __shfl_down(fs, d, 64);
+    fq += __shfl_down(fq, d, 64);
+  }
+  __shared__ double lds[2 * (FBLK / 64)];
+  int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  if (lane == 0) { lds[2 * wave] = fs; lds[2 * wave + 1] = fq; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double ts = 0.0, tq = 0.0;
+    for (int wv = 0; wv < FBLK / 64; ++wv) {
+      ts += lds[2 * wv]; tq += lds[2 * wv + 1];
+    }
+    atomicAdd(acc + 2 * k, ts);
+    atomicAdd(acc + 2 * k + 1, tq);
+  }
+}
+
+// k_clip_sgd_mb's `gv = g * scale; p -= lr * gv` as the operations it
+// compiles to: one rounded product, then ONE fma.  Written out, because
+// left to the compiler's contraction the unrolled tile code fused most of
+// its 32 updates per thread and left a few as multiply + subtract, one ulp
+// off wherever lr * gv is inexact.
+__device__ __forceinline__ float fc1t_update(float p, float g, float scale,
+                                             float lr) {
+  return fmaf(-lr, __fmul_rn(g, scale), p);
+}
+
+// W3 rows of one tile: the flat kernel's update on the tile's elements,
+// VEC adjacent columns per access
+template <int VEC>
+__device__ __forceinline__ void fc1t_apply(float* __restrict__ w3,
+                                           const f32x4 (&t)[2][4], int nblk,
+                                           float scale, float lr) {
+  int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  int il = lane & 15;
+  #pragma unroll
+  for (int tt = 0; tt < 2; ++tt) {
+    int j = w * 32 + tt * 16 + (lane >> 4) * 4;
+    #pragma unroll
+    for (int r = 0; r < 4; ++r)
+      #pragma unroll
+      for (int g = 0; g < 4 / VEC; ++g) {
+        float* p = w3 + ((j + r) * 9216 + nblk * 64 + FC1B_COL(VEC, g, il));
+        float v[VEC];
+        ld_vec<VEC>(p, v);
+        #pragma unroll
+        for (int e = 0; e < VEC; ++e)
+          v[e] = fc1t_update(v[e], t[tt][g * VEC + e][r], scale, lr);
+        st_vec<VEC>(p, v);
+      }
+  }
+}
+
+// grid = K * FC1T_REST_BLKS rest blocks (block 0 among them keeps the
+// clipped stats, as k_clip_sgd_mb's block 0), then K * 144 /
+// FC1T_CLIP_TILES tile blocks
+__global__ __launch_bounds__(FBLK)
+void k_fc1_tail_clip_sgd_mb(float* __restrict__ params,
+                            const float* __restrict__ grads, long long P,
+                            long long ow3, const float* __restrict__ dz3,
+                            const float* __restrict__ a2, int bs, int K,
+                            const double* __restrict__ acc, float max_norm,
+                            float eps, const float* __restrict__ lr_t,
+                            float* __restrict__ stats_out) {
+  constexpr int TB = 144 / FC1T_CLIP_TILES;
+  float lr = lr_t[0];
+  if (blockIdx.x == 0)
+    for (int k = threadIdx.x; k < K; k += blockDim.x) {
+      float scale = clip_scale(acc, k, max_norm, eps);
+      stats_out[2 * k] += scale * (float)acc[2 * k];
+      stats_out[2 * k + 1] += scale * scale * (float)acc[2 * k + 1];
+    }
+  if (blockIdx.x < K * FC1T_REST_BLKS) {
+    int k = blockIdx.x / FC1T_REST_BLKS;
+    int r = blockIdx.x % FC1T_REST_BLKS;
+    float scale = clip_scale(acc, k, max_norm, eps);
+    long long n = P - FC1T_W3N;
+    for (long long i = (long long)r * FBLK + threadIdx.x; i < n;
+         i += (long long)FC1T_REST_BLKS * FBLK) {
+      long long a = (long long)k * P + fc1t_rest_index(i, ow3);
+      params[a] = fc1t_update(params[a], grads[a], scale, lr);
+    }
+    return;
+  }
+  int tb = blockIdx.x - K * FC1T_REST_BLKS;
+  int k = tb / TB;
+  int r = tb % TB;
+  float scale = clip_scale(acc, k, max_norm, eps);
+  const float* dz = dz3 + (long long)k * bs * 128;
+  const float* a2k = a2 + (long long)k * bs * 9216;
+  float* w3 = params + (long long)k * P + ow3;
+  int vec = addr_vec((unsigned long long)a2k | (unsigned long long)w3);
+  for (int u = 0; u < FC1T_CLIP_TILES; ++u) {
+    int nblk = r * FC1T_CLIP_TILES + u;
+    f32x4 t[2][4];
+    fc1t_tile(dz, a2k, bs, nblk, vec, t);
+    if (vec == 4) fc1t_apply<4>(w3, t, nblk, scale, lr);
+    else if (vec == 2) fc1t_apply<2>(w3, t, nblk, scale, lr);
+    else fc1t_apply<1>(w3, t, nblk, scale, lr);
+  }
+}
+
+// the pair, for the mega round and the debug entry; acc[0 .. 2K) is zero
+// on entry
+static void fc1_fused_tail(float* params, const float* grads, long long P,
+                           long long ow3, const float* dz3, const float* a2,
+                           int bs, int K, double* acc, float max_norm,
+                           const float* lr_t, float* stats_out,
+                           hipStream_t s) {
+  hipLaunchKernelGGL(k_fc1_tail_sumsq_mb,
+                     dim3(K * (144 / FC1T_NORM_TILES + FC1T_REST_BLKS)),
+                     dim3(FBLK), 0, s, grads, P, ow3, dz3, a2, bs, K, acc);
+  hipLaunchKernelGGL(k_fc1_tail_clip_sgd_mb,
+                     dim3(K * (FC1T_REST_BLKS + 144 / FC1T_CLIP_TILES)),
+                     dim3(FBLK), 0, s, params, grads, P, ow3, dz3, a2, bs, K,
+                     acc, max_norm, 1e-6f, lr_t, stats_out);
 }
 
 // weighted pseudo-gradients + deterministic accumulate into round_accum
@@ -2057,7 +2298,7 @@ static void cnn_step(const float* shard_x, const long long* shard_y,
                      int K, int bs, int C, float* params, float* grads,
                      const CnnWorkspace& ws, double* acc, int n_acc,
                      float p1, float p2, float* loss_out, int use_bf16,
-                     hipStream_t s) {
+                     bool store_dw3, hipStream_t s) {
   CnnOffsets o = cnn_offsets(C);
   long long P = o.total;
   int G = K * bs;
@@ -2106,9 +2347,15 @@ static void cnn_step(const float* shard_x, const long long* shard_y,
        ws.a3, params, P, o.w4, o.b4, meta, bs, K, C, ws.yb, ws.dlogits,
        loss_out, ws.z3, ws.m3, p2, ws.dz3);
   STEP(k_fc2_bwd_w_mb, dim3(K * ((C * 128 + FBLK - 1) / FBLK)), dim3(FBLK), 0,
-       ws.dlogits, ws.a3, grads, P, o.w4, o.b4, bs, K, C);
-  STEP(k_fc1_bwd_w_mfma_mb, dim3(K * 144), dim3(FBLK), 0, ws.dz3, ws.a2,
-       grads, P, o.w3, grads, P, o.b3, bs, K);
+       ws.dlogits, ws.a3, grads, P, o.w4, o.b4, bs, K, C,
+       store_dw3 ? (const float*)nullptr : ws.dz3, o.b3);
+  // store_dw3 = false (the FedAvg / DGA mega round): dW3 is never stored,
+  // the caller's fc1_fused_tail re-forms it from ws.dz3 and ws.a2, which
+  // nothing below overwrites, and k_fc2_bwd_w_mb above wrote the bias sums
+  if (store_dw3) {
+    STEP(k_fc1_bwd_w_mfma_mb, dim3(K * 144), dim3(FBLK), 0, ws.dz3, ws.a2,
+         grads, P, o.w3, grads, P, o.b3, bs, K);
+  }
   STEP(k_fc1_bwd_x_mfma_mb, dim3(K * FC1X_BLKS), dim3(64 * FC1X_WAVES), 0,
        ws.dz3, params, P, o.w3, bs, K, ws.da2);
   STEP(k_pool_drop_bwd_bias_mb, dim3(K * 64), dim3(FBLK), 0, ws.da2, ws.pidx,
@@ -2157,7 +2404,7 @@ extern "C" void launch_cnn_epoch(
     cnn_step(shard_x, shard_y, order, StepMetaOne{row_base, start, B, seed},
              it, K, B, C, params, grads, ws,
              prox ? ws.red_partials : ws.red_acc, prox ? 3 : 2, p1, p2,
-             loss_acc, use_bf16, s);
+             loss_acc, use_bf16, /*store_dw3=*/true, s);
     if (prox) {
       // FedProx: the PROX pair at K = 1, every step active; forms
       // g + mu (w - w_g) in registers and adds the regulariser to loss_acc
@@ -2252,10 +2499,11 @@ extern "C" void launch_cnn_round_mega(
              StepMetaDev{row_bases_dev, order_offs_dev, counts_dev, seeds_dev,
                          t},
              t, K, bs, C, params_stack, grads_stack, ws, acc2k,
-             prox ? 3 * K : 2 * K, p1, p2, loss_out, use_bf16, s);
+             prox ? 3 * K : 2 * K, p1, p2, loss_out, use_bf16,
+             /*store_dw3=*/prox, s);
     // acc2k was zeroed by this step's k_gather_mb
-    int blocks_per_k = (int)((P + SUMSQ_CHUNK - 1) / SUMSQ_CHUNK);
     if (prox) {
+      int blocks_per_k = (int)((P + SUMSQ_CHUNK - 1) / SUMSQ_CHUNK);
       // same two dispatches; idle clients (t * bs >= counts[k]) get no
       // proximal term and no regulariser
       ProxArgs px{params_stack, K, server_params, mu, counts_dev, t, bs,
@@ -2268,12 +2516,10 @@ extern "C" void launch_cnn_round_mega(
                          acc2k, max_norm, 1e-6f, lr_t, stats_out, px);
       continue;
     }
-    hipLaunchKernelGGL(k_sumsq_mb<NoProx>, dim3(K * blocks_per_k),
-                       dim3(FBLK), 0, s, grads_stack, P, blocks_per_k, acc2k,
-                       NoProx{});
-    hipLaunchKernelGGL((k_clip_sgd_mb<false, NoProx>), dim3(gkp), dim3(FBLK),
-                       0, s, params_stack, grads_stack, P, K, acc2k, max_norm,
-                       1e-6f, lr_t, stats_out, NoProx{});
+    // FedAvg / DGA: norm and clip + SGD with dW3 re-formed from the
+    // step's dz3 and a2 (FedProx keeps the stored path above)
+    fc1_fused_tail(params_stack, grads_stack, P, cnn_offsets(C).w3, ws.dz3,
+                   ws.a2, bs, K, acc2k, max_norm, lr_t, stats_out, s);
   }
   if (dga) {
     dga_tail(params_stack, server_params, P, K, loss_out, stats_out,
@@ -2429,6 +2675,17 @@ void launch_fc1_bwd_w_mfma(const float* dz3, const float* a2, int bs, int K,
                            float* dw3, float* db3, hipStream_t s) {
   hipLaunchKernelGGL(k_fc1_bwd_w_mfma_mb, dim3(K * 144), dim3(FBLK), 0, s,
                      dz3, a2, dw3, W3N, 0LL, db3, 128LL, 0LL, bs, K);
+}
+// the fused fc1 tail on K-stacked arenas of the C-class CNN: zero acc,
+// norm pass, clip + SGD pass
+void launch_fc1_fused_tail(float* params, const float* grads,
+                           const float* dz3, const float* a2, int bs, int K,
+                           int C, double* acc, float max_norm,
+                           const float* lr_t, float* stats, hipStream_t s) {
+  CnnOffsets o = cnn_offsets(C);
+  hipMemsetAsync(acc, 0, 2 * K * sizeof(double), s);
+  fc1_fused_tail(params, grads, o.total, o.w3, dz3, a2, bs, K, acc, max_norm,
+                 lr_t, stats, s);
 }
 void launch_fc1_bwd_x_mfma(const float* dz3, const float* w3, int bs, int K,
                            float* da2, hipStream_t s) {

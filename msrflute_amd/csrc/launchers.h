@@ -356,6 +356,13 @@ void launch_fc1_bwd_w_mfma(const float* dz3, const float* a2, int bs, int K,
                            float* dw3, float* db3, hipStream_t s);
 void launch_fc1_bwd_x_mfma(const float* dz3, const float* w3, int bs, int K,
                            float* da2, hipStream_t s);
+// The fused fc1 tail of the FedAvg mega round on [K * P] stacks (P from C):
+// zeroes acc[0 .. 2K), sums the gradient with dW3 re-formed from dz3 and
+// a2, then clips and applies it.  The W3 segment of grads is never read.
+void launch_fc1_fused_tail(float* params, const float* grads,
+                           const float* dz3, const float* a2, int bs, int K,
+                           int C, double* acc, float max_norm,
+                           const float* lr_t, float* stats, hipStream_t s);
 void launch_mfma_bf16_probe(const void* A, const void* B, float* D,
                             hipStream_t s);
 void launch_fc1_fwd_mfma_bf16(const float* a2, const float* w3,
